@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark (BASELINE.json): 127-tap complex<float> FIR, decimate-by-4, 64 M samples per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,8 +12,14 @@ torch.distributed is used only for the barrier and the max-over-ranks timing red
 
 Rank 0 prints ONE JSON line: value = input samples processed by all ranks / max-over-ranks wall
 time of the K timed steps (Msamples/s), plus a `roofline` object for the FIR kernel (algorithmic
-bytes per launch / mean launch time from HIP events on the launch stream) and a `cpu_baseline`
-object (the C oracle timed on this host, N = 1 only).
+bytes per launch / mean launch time from HIP events on the launch stream).
+
+A plain run does only that: set up, warm up (W steps and the clock settle), time the K steps, print.
+--dump-outputs DIR also writes what the last timed step's call returned (dump_outputs). --full adds
+every other leg, each a run of its own after the timed region: the one-output-buffer and probes-build
+ceilings of the roofline, the `secondary` configs (or, N > 1, the config-4 FM leg) and the
+`cpu_baseline` object (the C oracle timed on this host, N = 1 only); --no-secondary and
+--no-cpu-baseline drop the last two from a --full run.
 """
 from __future__ import annotations
 
@@ -37,6 +43,7 @@ HBM_ACHIEVABLE_GBPS = 6300.0  # MI355X_MICROARCH.md, "HBM [CDNA4]": ~6.3 TB/s ac
 PMC_SUMMARY = os.path.join(ROOT, "profiles", "pmc_fir_fc_d4.json")
 ROTATE = 3  # input batches cycled through (see main)
 CPU_SAMPLE_S = 10.0  # wall seconds of CPU-baseline work (bounded sample of the workload)
+DUMP_SAMPLE, DUMP_EDGE, DUMP_SEED = 1 << 20, 4096, 0xD0C5  # --dump-outputs: outputs kept of the step's 2^24
 
 
 def dist_env():
@@ -74,6 +81,32 @@ def barrier():
 def aggregate(samples_per_rank: int, world: int, steps: int, seconds_max: float) -> float:
     """Whole-job Msamples/s: every rank's input samples over the slowest rank's wall time."""
     return samples_per_rank * world * steps / seconds_max / 1e6
+
+
+def dump_indices(n_out: int):
+    """The output indices --dump-outputs keeps: the first and last DUMP_EDGE outputs and DUMP_SAMPLE drawn
+    from a fixed seed, sorted, each once. The same for every run and every build."""
+    import numpy as np
+
+    edge = min(DUMP_EDGE, n_out)
+    idx = np.concatenate([np.arange(edge), np.arange(n_out - edge, n_out),
+                          np.random.default_rng(DUMP_SEED).integers(0, n_out, DUMP_SAMPLE)])
+    return np.unique(idx.astype(np.int64))
+
+
+def dump_outputs(torch, dirname, name, y):
+    """--dump-outputs: the complex outputs a caller of the timed gsdrFirFC call receives, as written by the
+    last timed step. The whole output is 134 MB, so DIR/<name>.npy holds the outputs at dump_indices() as
+    float32 rows (re, im) -- the bits the kernel wrote -- and DIR/<name>_index.npy those indices (float64,
+    exact). The inputs come from a seeded generator and the last step's batch is fixed by K alone (main), so
+    two runs with the same arguments dump the outputs of the same call on the same input."""
+    import numpy as np
+
+    idx = dump_indices(y.numel())
+    vals = torch.view_as_real(y[torch.from_numpy(idx).to(y.device)]).cpu().numpy()
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(vals, dtype=np.float32))
+    np.save(os.path.join(dirname, name + "_index.npy"), idx.astype(np.float64))
 
 
 def load_pmc_traffic():
@@ -819,9 +852,15 @@ def main():
     ap.add_argument("--variant", type=int, default=-1, help="FC/D=4 tile shape (gsdrxFirFCVariant), -1 = default")
     ap.add_argument("--settle-max", type=int, default=600,
                     help="max extra untimed launches while the clock ramps (0 = off); reported as clock_settle_launches")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (a fixed seeded sample) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline: roofline ceilings, secondary configs, CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary configs")
     args = ap.parse_args()
+    secondary = args.full and not args.no_secondary
+    cpu_baseline = args.full and not args.no_cpu_baseline
     # BENCH_REHEARSE=1 (rehearsal only, never a reported number): gloo instead of RCCL and rank r on
     # cuda:(r mod device_count), so the N > 1 code path can run on a one-GPU box with ranks sharing it.
     rehearse = os.environ.get("BENCH_REHEARSE") == "1"
@@ -903,6 +942,12 @@ def main():
         step()
     torch.cuda.synchronize()
     settle = settle_clocks(torch, step, args.settle_max) if args.settle_max > 0 else 0
+    # the settle ends when the clock does, after a number of launches that differs from run to run: go on to the
+    # end of the batch cycle, so the timed steps start at batch 0 and step k's input and output buffers depend on
+    # k alone (--dump-outputs: the same call's output in every run)
+    while counter[0] % ROTATE:
+        step()
+        settle += 1
     barrier()
     solo_fir_s = None
     if world > 1:
@@ -918,6 +963,8 @@ def main():
             return a.elapsed_time(b) / args.steps * 1e-3
 
         solo_fir_s = time_solo(torch, rank, fir_k)
+        while counter[0] % ROTATE:  # rank 0's solo launches moved it along the cycle: back to batch 0
+            step()
 
     # One HIP event pair around the K timed launches, on the launch stream: an event record between
     # launches is itself a ~10 us GPU command (timestamp + cache flush) and would inflate both numbers.
@@ -936,8 +983,12 @@ def main():
     kern_s = ev0.elapsed_time(ev1) / args.steps * 1e-3  # mean launch duration (back-to-back launches)
     kern_s_max = reduce_max(kern_s, device)
     per_rank = gather_rows(torch, [kern_s, wall], rank, world, device)
+    if args.dump_outputs and args.steps > 0:
+        # before any other leg writes these buffers again
+        dump_outputs(torch, args.dump_outputs, "fir_fc_out" if world == 1 else f"fir_fc_out_rank{rank}",
+                     ys[(counter[0] - 1) % ROTATE])
     fm_multi = None
-    if world > 1 and not args.no_secondary:
+    if world > 1 and secondary:
         fm_multi = fm_multi_gpu(torch, device, taps, rank, world, args.steps)
 
     if rank != 0:
@@ -955,6 +1006,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(wall_max / args.steps * 1e3, 4),
         "higher_is_better": True,
         "scaling": "weak",
@@ -1003,7 +1055,7 @@ def main():
         line["roofline"]["traffic_source"] = os.path.relpath(PMC_SUMMARY, ROOT)
     line["roofline"]["guide_achievable_gbps"] = HBM_ACHIEVABLE_GBPS
     line["roofline"]["frac_of_guide_achievable"] = round(achieved / HBM_ACHIEVABLE_GBPS, 4)
-    if world == 1 and not args.no_secondary:
+    if world == 1 and secondary:
         # the round-5 measurement (every step writing the same output buffer) beside the rotated one: what the
         # 256 MB Infinity Cache had been worth to the headline figure
         one_y = [(DECIM, taps.data_ptr(), TAPS, xb.data_ptr(), y.data_ptr(), N_OUT, dev_index, stream) for xb in xs]
@@ -1030,11 +1082,11 @@ def main():
                           "without the multiply-adds; 104: the multiply-adds without the staging",
             }
     c5 = None
-    if world == 1 and not args.no_secondary:
+    if world == 1 and secondary:
         line["secondary"], c5 = secondary_configs(torch, ops, device, taps)
     if fm_multi is not None:
         line["secondary"] = {"fm_chain_multi_gpu": fm_multi}
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and cpu_baseline:
         threads, how = host_cores()
         build = native_oracle()
         per = cpu_baselines(x.cpu().numpy(), taps_np, threads, c5)

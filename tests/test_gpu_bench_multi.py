@@ -31,7 +31,7 @@ def test_bench_two_ranks_rehearsal(cuda, launcher):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     args = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--settle-max", "50",
-            "--no-cpu-baseline"]
+            "--full", "--no-cpu-baseline"]  # --full: the config-4 FM record is a leg of its own
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                "--master-addr", "127.0.0.1", "--master-port", str(free_port())] + args

@@ -8,6 +8,8 @@
 #   prof[:<args>]         rocprofv3 --kernel-trace --stats of python bench.py <args>
 #   pmc[:<args>]          tools/pmc.sh of python bench.py --steps 3 --warmup 1 --no-secondary --no-cpu-baseline <args>
 #   py:<script> [args]    python <script> <args>
+# bench.py alone times the headline only; its secondary configs, roofline ceilings and CPU baselines need
+# "bench:--full" / "prof:--full ...".
 tag=$1; shift
 mkdir -p gpurun_out
 export TMPDIR=/tmp

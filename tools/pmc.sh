@@ -2,6 +2,7 @@
 # usage: tools/pmc.sh <outdir-under-gpurun_out> <command...>
 # rocprofv3 kernel-trace/stats pass, then separate PMC passes (never combined with tracing).
 out=gpurun_out/$1; shift
+[ -n "$PMC_OUT_ROOT" ] && out=$PMC_OUT_ROOT/${out#*/}  # another root directory for <outdir>
 mkdir -p "$out"
 export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- "$@" > "$out/trace.log" 2>&1 || { echo "trace pass failed"; exit 1; }
