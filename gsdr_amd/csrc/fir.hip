@@ -132,28 +132,9 @@ hipError_t launch_fc_probe(const FirJob&, hipStream_t) { return hipErrorInvalidV
 #endif  // GSDR_TUNING_PROBES
 
 // The streaming object's one-launch FIR step on complex float samples (stream.hip; stream_step_tiled).
-hipError_t fir_fc_stream_step(size_t decimation, const float* taps, size_t tapCount, const hipFloatComplex* chunk,
-                              uint64_t chunkLen, int64_t inOff, const hipFloatComplex* hist, uint64_t histLen,
-                              hipFloatComplex* histOut, int64_t histFrom, uint64_t histN, hipFloatComplex* output,
-                              size_t numOutputs, int32_t device, hipStream_t stream) {
-  FirJob job;
-  job.in = chunk;
-  job.taps = taps;
-  job.out = output;
-  job.D = decimation;
-  job.T = tapCount;
-  job.N = numOutputs;
-  job.L = chunkLen;
-  job.mode = kModeFir;
-  job.in_off = inOff;
-  job.hist = hist;
-  job.hist_len = histLen;
-  job.hist_out = histOut;
-  job.hist_from = histFrom;
-  job.hist_n = histN;
-  DeviceScope scope(device);
-  if (scope.status() != hipSuccess) return scope.status();
-  return stream_step_tiled<float2, kModeFir>(job, stream);
+hipError_t fir_fc_stream_step(size_t decimation, const float* taps, size_t tapCount, const StreamOperands& so,
+                              hipFloatComplex* output, size_t numOutputs, int32_t device, hipStream_t stream) {
+  return fir_stream_step_tiled<float2>(decimation, taps, tapCount, so, output, numOutputs, device, stream);
 }
 
 }  // namespace gsdr

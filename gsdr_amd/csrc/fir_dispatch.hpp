@@ -40,17 +40,29 @@ struct FirJob {
   uint32_t out_phase = 0;  // absolute index of output 0 mod 16 (fir_i8_mfma.hpp)
   uint64_t q0 = 0;         // chains: absolute index of output 0 (firstSampleIndex / D) -- the anchored
                            // polyphase tiles' NCO cell grid (fir_engine.hpp, stage_tile_rel)
-  // the int8 matrix-core kernels' streaming inputs (FirParams)
-  int64_t in_off = 0;
-  const void* hist = nullptr;
-  uint64_t hist_len = 0;
-  void* hist_out = nullptr;
-  int64_t hist_from = 0;
-  uint64_t hist_n = 0;
+  // a streaming step's operands (FirParams): `in` is then the chunk and L its length. All zero otherwise.
+  StreamOperands step{};
   // the streaming object's one-launch path on the tiled kernels (stream_step_tiled): only the polyphase and
   // contiguous-window kernels take it; the others return hipErrorNotSupported before launching anything
   bool stream_tiled = false;
+
+  void set_step(const StreamOperands& so) {
+    step = so;
+    in = so.chunk;
+    L = so.chunk_len;
+  }
 };
+
+// The fields every job has, FIR or chain: the filter, where the outputs go and how many there are.
+inline FirJob fir_job(size_t D, const void* taps, size_t T, void* out, size_t N) {
+  FirJob j;
+  j.D = D;
+  j.taps = taps;
+  j.T = T;
+  j.out = out;
+  j.N = N;
+  return j;
+}
 
 // LDS budget per workgroup for the tiled kernels (keeps >= 2 workgroups per CU on 160 KiB).
 constexpr size_t kMaxTileLds = 64 * 1024;
@@ -68,12 +80,12 @@ inline FirParams make_params(const FirJob& j) {
   p.nco_n0 = j.nco_n0;
   p.fm_gain = j.fm_gain;
   p.out_phase = j.out_phase & 15u;
-  p.in_off = j.in_off;
-  p.hist = j.hist;
-  p.hist_len = j.hist_len;
-  p.hist_out = j.hist_out;
-  p.hist_from = j.hist_from;
-  p.hist_n = j.hist_n;
+  p.in_off = j.step.in_off;
+  p.hist = j.step.hist;
+  p.hist_len = j.step.hist_len;
+  p.hist_out = j.step.hist_out;
+  p.hist_from = j.step.hist_from;
+  p.hist_n = j.step.hist_n;
   return p;
 }
 
@@ -118,6 +130,35 @@ inline void launch_shifted(const void* in, F&& f) {
   }
 }
 
+// The staging of a tiled launch whose tiles start every tile_samples samples from `in`: aligned vector loads
+// (VEC) when the pointer and the tile stride allow, else shifted aligned loads (SH > 0), else per-sample
+// loads. Calls f(std::bool_constant<VEC>, std::integral_constant<int, SH>), which launches the kernel.
+template <class InT, class F>
+inline void with_staging(const void* in, uint64_t tile_samples, F&& f) {
+  constexpr uint64_t A = SampleT<InT>::kSrcAlign;
+  constexpr std::integral_constant<int, 0> kNoShift{};
+  if ((reinterpret_cast<uintptr_t>(in) % A) == 0 && (tile_samples * sizeof(InT)) % A == 0) {
+    f(std::true_type{}, kNoShift);
+  } else if (shifted_staging<InT>(in, tile_samples)) {
+    launch_shifted<InT>(in, [&](auto sh) { f(std::false_type{}, sh); });
+  } else {
+    f(std::false_type{}, kNoShift);
+  }
+}
+
+// Tap chunks and LDS bytes of a tile whose taps lie in rows of `row` taps, rows_per_chunk rows a chunk (the
+// polyphase kernels: rows of D, JC a chunk; the contiguous-window kernel: IC single taps a chunk). False
+// when the span does not fit a tile; the caller then has its own fallback.
+template <class InT, int D, int R, int WG, int MODE>
+inline bool tap_span(size_t T, uint64_t row, uint64_t rows_per_chunk, uint32_t* nch, size_t* lds) {
+  const uint64_t n = ceil_div<uint64_t>(ceil_div<uint64_t>(T, row), rows_per_chunk);
+  const uint64_t span = n * rows_per_chunk * row;
+  if (span > 0x40000000ull) return false;
+  *nch = (uint32_t)n;
+  *lds = poly_lds_bytes<InT, D, R, WG>((uint32_t)span, MODE);
+  return *lds <= kMaxTileLds;
+}
+
 template <class TapT, class InT, int MODE>
 hipError_t launch_generic(const FirJob& j, hipStream_t s) {
   if (j.stream_tiled) return hipErrorNotSupported;
@@ -153,31 +194,16 @@ template <class TapT, class InT, int D, int R, int JC, int WG, int MODE, int ABL
 hipError_t launch_poly(const FirJob& j, hipStream_t s) {
   using Geo = TileGeo<InT, D, R, WG>;
   FirParams p = make_params(j);
-  const uint64_t rows = ceil_div<uint64_t>(j.T, (uint64_t)D);
-  const uint64_t nch = ceil_div<uint64_t>(rows, (uint64_t)JC);
-  const uint64_t span = nch * JC * D;
-  if (span > 0x40000000ull) return launch_generic<TapT, InT, MODE>(j, s);
-  const size_t lds = poly_lds_bytes<InT, D, R, WG>((uint32_t)span, MODE);
-  if (lds > kMaxTileLds) return launch_generic<TapT, InT, MODE>(j, s);
-  p.nch = (uint32_t)nch;
+  size_t lds = 0;
+  if (!tap_span<InT, D, R, WG, MODE>(j.T, D, JC, &p.nch, &lds)) return launch_generic<TapT, InT, MODE>(j, s);
   const uint64_t tiles = poly_grid<MODE>(j, p, Geo::KT, R, SUBS);
-  const uint32_t stride = p.tile_stride;
   if (tiles > 0x7fffffffull) return hipErrorInvalidValue;
-  constexpr uint64_t A = SampleT<InT>::kSrcAlign;
   // (the anchored grid moves every tile start by tile_shift * D samples: a whole number of aligned units, D even)
-  const bool vec = (reinterpret_cast<uintptr_t>(j.in) % A) == 0 && ((uint64_t)stride * D * sizeof(InT)) % A == 0;
-  if (vec) {
-    k_fir_poly<TapT, InT, D, R, JC, WG, true, MODE, ABL, NT, XM, CST, DMA, 0, SUBS>
+  with_staging<InT>(j.in, (uint64_t)p.tile_stride * D, [&](auto vec, auto sh) {
+    constexpr int SH = decltype(sh)::value;  // the shifted loads have no LDS-DMA form
+    k_fir_poly<TapT, InT, D, R, JC, WG, decltype(vec)::value, MODE, ABL, NT, XM, CST, (SH == 0 && DMA), SH, SUBS>
         <<<dim3((uint32_t)tiles), dim3(WG), lds, s>>>(p);
-  } else if (shifted_staging<InT>(j.in, (uint64_t)stride * D)) {
-    launch_shifted<InT>(j.in, [&](auto sh) {
-      k_fir_poly<TapT, InT, D, R, JC, WG, false, MODE, ABL, NT, XM, CST, false, decltype(sh)::value, SUBS>
-          <<<dim3((uint32_t)tiles), dim3(WG), lds, s>>>(p);
-    });
-  } else {
-    k_fir_poly<TapT, InT, D, R, JC, WG, false, MODE, ABL, NT, XM, CST, DMA, 0, SUBS>
-        <<<dim3((uint32_t)tiles), dim3(WG), lds, s>>>(p);
-  }
+  });
   return launch_status();
 }
 
@@ -203,28 +229,16 @@ template <class TapT, class InT, int D, int R, int IC, int WG, int MODE>
 hipError_t launch_contig(const FirJob& j, hipStream_t s) {
   using Geo = TileGeo<InT, D, R, WG>;
   FirParams p = make_params(j);
-  const uint64_t nch = ceil_div<uint64_t>(j.T, (uint64_t)IC);
-  const uint64_t span = nch * IC;
-  if (span > 0x40000000ull) return launch_generic<TapT, InT, MODE>(j, s);
-  const size_t lds = poly_lds_bytes<InT, D, R, WG>((uint32_t)span, MODE);
-  if (lds > kMaxTileLds) return launch_generic<TapT, InT, MODE>(j, s);
-  p.nch = (uint32_t)nch;
+  size_t lds = 0;
+  if (!tap_span<InT, D, R, WG, MODE>(j.T, 1, IC, &p.nch, &lds)) return launch_generic<TapT, InT, MODE>(j, s);
   const uint32_t stride = (MODE == kModeFm) ? fm_tile_stride<InT>(Geo::KT, j.D) : Geo::KT;
   p.tile_stride = stride;
   const uint64_t tiles = ceil_div<uint64_t>(j.N, stride);
   if (tiles > 0x7fffffffull) return hipErrorInvalidValue;
-  constexpr uint64_t A = SampleT<InT>::kSrcAlign;
-  const bool vec = (reinterpret_cast<uintptr_t>(j.in) % A) == 0 && ((uint64_t)stride * D * sizeof(InT)) % A == 0;
-  if (vec) {
-    k_fir_contig<TapT, InT, D, R, IC, WG, true, MODE><<<dim3((uint32_t)tiles), dim3(WG), lds, s>>>(p);
-  } else if (shifted_staging<InT>(j.in, (uint64_t)stride * D)) {
-    launch_shifted<InT>(j.in, [&](auto sh) {
-      k_fir_contig<TapT, InT, D, R, IC, WG, false, MODE, decltype(sh)::value>
-          <<<dim3((uint32_t)tiles), dim3(WG), lds, s>>>(p);
-    });
-  } else {
-    k_fir_contig<TapT, InT, D, R, IC, WG, false, MODE><<<dim3((uint32_t)tiles), dim3(WG), lds, s>>>(p);
-  }
+  with_staging<InT>(j.in, (uint64_t)stride * D, [&](auto vec, auto sh) {
+    k_fir_contig<TapT, InT, D, R, IC, WG, decltype(vec)::value, MODE, decltype(sh)::value>
+        <<<dim3((uint32_t)tiles), dim3(WG), lds, s>>>(p);
+  });
   return launch_status();
 }
 
@@ -293,30 +307,17 @@ hipError_t launch_d4_complex(const FirJob& j, hipStream_t s) {
 template <class TapT, class InT, int D, int R, int JC, int WG, int MODE>
 hipError_t launch_multi_grouped(const FirJob& j, const MultiParams& mp, hipStream_t s) {
   using Geo = TileGeo<InT, D, R, WG>;
+  static_assert(!std::is_same<InT, float>::value, "complex or int8 I/Q samples: one shifted form");
   FirParams p = make_params(j);
-  const uint64_t rows = ceil_div<uint64_t>(j.T, (uint64_t)D);
-  const uint64_t nch = ceil_div<uint64_t>(rows, (uint64_t)JC);
-  const uint64_t span = nch * JC * D;
-  if (span > 0x40000000ull) return hipErrorNotSupported;
-  const size_t lds = poly_lds_bytes<InT, D, R, WG>((uint32_t)span, MODE);
-  if (lds > kMaxTileLds) return hipErrorNotSupported;
-  p.nch = (uint32_t)nch;
+  size_t lds = 0;
+  if (!tap_span<InT, D, R, WG, MODE>(j.T, D, JC, &p.nch, &lds)) return hipErrorNotSupported;
   const uint64_t tiles = poly_grid<MODE>(j, p, Geo::KT, R, 1);
-  const uint32_t stride = p.tile_stride;
   const uint64_t blocks = ceil_div<uint64_t>(tiles, 8) * 8 * mp.count;
   if (blocks > 0x7fffffffull) return hipErrorNotSupported;
-  constexpr uint64_t A = SampleT<InT>::kSrcAlign;
-  const bool vec = (reinterpret_cast<uintptr_t>(j.in) % A) == 0 && ((uint64_t)stride * D * sizeof(InT)) % A == 0;
-  if (vec) {
-    k_fir_poly_grouped<TapT, InT, D, R, JC, WG, true, MODE, 0><<<dim3((uint32_t)blocks), dim3(WG), lds, s>>>(
-        p, mp, (uint32_t)tiles);
-  } else if (shifted_staging<InT>(j.in, (uint64_t)stride * D)) {
-    k_fir_poly_grouped<TapT, InT, D, R, JC, WG, false, MODE, 1><<<dim3((uint32_t)blocks), dim3(WG), lds, s>>>(
-        p, mp, (uint32_t)tiles);
-  } else {
-    k_fir_poly_grouped<TapT, InT, D, R, JC, WG, false, MODE, 0><<<dim3((uint32_t)blocks), dim3(WG), lds, s>>>(
-        p, mp, (uint32_t)tiles);
-  }
+  with_staging<InT>(j.in, (uint64_t)p.tile_stride * D, [&](auto vec, auto sh) {
+    k_fir_poly_grouped<TapT, InT, D, R, JC, WG, decltype(vec)::value, MODE, decltype(sh)::value>
+        <<<dim3((uint32_t)blocks), dim3(WG), lds, s>>>(p, mp, (uint32_t)tiles);
+  });
   return launch_status();
 }
 
@@ -344,7 +345,7 @@ hipError_t launch_i8_mfma_nct(const FirJob& j, const FirParams& p, uint32_t ns, 
                               hipStream_t s) {
   using C = I8Mfma<D, NS, NCT>;
   // tile starts are at sample (j KT - phase) D + in_off: byte offset 2 D (j KT - phase) + 2 in_off
-  const uintptr_t in0 = reinterpret_cast<uintptr_t>(j.in) + (uintptr_t)(2 * j.in_off) - 2u * D * p.out_phase;
+  const uintptr_t in0 = reinterpret_cast<uintptr_t>(j.in) + (uintptr_t)(2 * p.in_off) - 2u * D * p.out_phase;
   const bool oa = ((reinterpret_cast<uintptr_t>(j.out) - 8u * p.out_phase) % 16) == 0;
 #define GSDR_I8_LAUNCH(G, LM)                                                                                     \
   (oa ? (k_fir_i8_mfma<D, NS, G, LM, true, BPC, NCT, PF><<<dim3(grid), dim3(C::WG), 0, s>>>(p, ns, (uint32_t)tiles), 0) \
@@ -408,7 +409,7 @@ hipError_t launch_chain_i8_mfma_nct(const FirJob& j, const FirParams& p, uint32_
                                     hipStream_t s) {
   using C = I8ChainMfma<MODE, NCT>;
   // tile starts are at sample 4 (j STRIDE - phase) + in_off: 8 (j STRIDE - phase) + 2 in_off bytes
-  const uintptr_t in0 = reinterpret_cast<uintptr_t>(j.in) + (uintptr_t)(2 * j.in_off);
+  const uintptr_t in0 = reinterpret_cast<uintptr_t>(j.in) + (uintptr_t)(2 * p.in_off);
   if (in0 % 8 == 0) {
     k_chain_i8_mfma<MODE, 1, BPC, NCT><<<dim3(grid), dim3(C::WG), 0, s>>>(p, ns, (uint32_t)tiles);
   } else if (in0 % 2 == 0) {  // 2-byte aligned: shifted 8-byte loads
@@ -561,20 +562,15 @@ hipError_t launch_rt_wg(const FirJob& j, uint32_t nch, size_t lds, hipStream_t s
   p.tile_stride = stride;
   const uint64_t tiles = ceil_div<uint64_t>(j.N, stride);
   if (tiles > 0x7fffffffull) return hipErrorInvalidValue;
-  constexpr uint64_t A = SampleT<InT>::kSrcAlign;
-  const bool vec = (reinterpret_cast<uintptr_t>(j.in) % A) == 0 && ((uint64_t)stride * j.D * sizeof(InT)) % A == 0;
   const dim3 grid((uint32_t)tiles), block(WG);
-  if (j.D % 2 == 0) {  // paired LDS reads (k_fir_rt): same products, same order
-    if (vec) {
-      k_fir_rt<TapT, InT, IC, WG, true, MODE, true><<<grid, block, lds, s>>>(p);
+  // (this kernel has no shifted form: both non-vector stagings load per sample)
+  with_staging<InT>(j.in, (uint64_t)stride * j.D, [&](auto vec, auto) {
+    if (j.D % 2 == 0) {  // paired LDS reads (k_fir_rt): same products, same order
+      k_fir_rt<TapT, InT, IC, WG, decltype(vec)::value, MODE, true><<<grid, block, lds, s>>>(p);
     } else {
-      k_fir_rt<TapT, InT, IC, WG, false, MODE, true><<<grid, block, lds, s>>>(p);
+      k_fir_rt<TapT, InT, IC, WG, decltype(vec)::value, MODE><<<grid, block, lds, s>>>(p);
     }
-  } else if (vec) {
-    k_fir_rt<TapT, InT, IC, WG, true, MODE><<<grid, block, lds, s>>>(p);
-  } else {
-    k_fir_rt<TapT, InT, IC, WG, false, MODE><<<grid, block, lds, s>>>(p);
-  }
+  });
   return launch_status();
 }
 
@@ -737,19 +733,25 @@ hipError_t launch_fir(const FirJob& j, hipStream_t s) {
   }
 }
 
-// The streaming object's one-launch step on the tiled kernels (stream.hip): outputs [0, N) of the call,
-// output 0's window at chunk offset j.in_off (negative: it starts in the history j.hist of j.hist_len
-// samples), the next history (chunk offsets [hist_from, + hist_n)) copied by workgroup 0 of the same
-// launch. j.in is the chunk and j.L its length here. The kernels are the monolithic call's, tile for tile,
-// so the outputs are bit-identical to it. hipErrorNotSupported (nothing launched) when the shape runs
-// another kernel; the stream then takes its seam path.
-template <class InT, int MODE>
-hipError_t stream_step_tiled(FirJob j, hipStream_t s) {
-  if (j.N == 0 || j.T == 0 || j.taps == nullptr || j.T > (1u << 26)) return hipErrorNotSupported;
+// A streaming step as the tiled kernels take it (FirParams): `in` is output 0's window, not the chunk.
+template <class InT>
+inline void set_step_tiled(FirJob& j, const StreamOperands& so) {
+  j.step = so;
   j.stream_tiled = true;
-  j.variant = -1;
-  j.in = static_cast<const InT*>(j.in) + j.in_off;  // output 0's window (may precede the chunk)
-  j.L = (uint64_t)((int64_t)j.L - j.in_off);         // samples readable from there
+  j.in = static_cast<const InT*>(so.chunk) + so.in_off;  // (may precede the chunk)
+  j.L = (uint64_t)((int64_t)so.chunk_len - so.in_off);   // samples readable from there
+}
+
+// The streaming object's one-launch step on the tiled kernels (stream.hip): outputs [0, N) of the call,
+// output 0's window at chunk offset so.in_off (negative: it starts in the history so.hist of so.hist_len
+// samples), the next history (chunk offsets [hist_from, + hist_n)) copied by workgroup 0 of the same
+// launch. The kernels are the monolithic call's, tile for tile, so the outputs are bit-identical to it.
+// hipErrorNotSupported (nothing launched) when the shape runs another kernel; the stream then takes its
+// seam path.
+template <class InT, int MODE>
+hipError_t stream_step_tiled(FirJob j, const StreamOperands& so, hipStream_t s) {
+  if (j.N == 0 || j.T == 0 || j.taps == nullptr || j.T > (1u << 26)) return hipErrorNotSupported;
+  set_step_tiled<InT>(j, so);
   return launch_fir<float, InT, MODE>(j, s);
 }
 

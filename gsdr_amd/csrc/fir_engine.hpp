@@ -34,6 +34,8 @@
 #include <type_traits>
 #include <utility>
 
+#include "stream_step.hpp"
+
 namespace gsdr {
 
 // ------------------------------------------------------------------------------------------------
@@ -179,8 +181,7 @@ __device__ __forceinline__ float2 tap_at<float2>(const TapBuf& tb, int i) {
 // ------------------------------------------------------------------------------------------------
 // Launch parameters (one struct for every mode; passed by value)
 // ------------------------------------------------------------------------------------------------
-enum Mode : int { kModeFir = 0, kModeFm = 1, kModeAm = 2 };
-
+// (enum Mode { kModeFir, kModeFm, kModeAm }: stream_step.hpp)
 struct FirParams {
   const void* in;
   const void* taps;

@@ -25,19 +25,25 @@ inline hipError_t fir_entry(size_t decimation, const TapT* taps, size_t tapCount
                      return st != hipSuccess ? st : launch_status();
                    }
                    if (taps == nullptr || input == nullptr) return hipErrorInvalidValue;
-                   FirJob job;
+                   FirJob job = fir_job(decimation, taps, tapCount, output, numOutputs);
                    job.in = input;
-                   job.taps = taps;
-                   job.out = output;
-                   job.D = decimation;
-                   job.T = tapCount;
-                   job.N = numOutputs;
                    job.L = (numOutputs - 1) * decimation + tapCount;
-                   job.mode = kModeFir;
                    job.variant = variant;
                    job.out_phase = out_phase;
                    return launch_fir<TapT, InT, kModeFir>(job, stream);
                  })());
+}
+
+// The streaming object's one-launch FIR step on the tiled kernels (stream.hip; stream_step_tiled): the exact
+// path, as the monolithic call runs for those shapes.
+template <class InT>
+inline hipError_t fir_stream_step_tiled(size_t decimation, const float* taps, size_t tapCount, const StreamOperands& so,
+                                        hipFloatComplex* output, size_t numOutputs, int32_t device,
+                                        hipStream_t stream) {
+  const FirJob job = fir_job(decimation, taps, tapCount, output, numOutputs);
+  DeviceScope scope(device);
+  if (scope.status() != hipSuccess) return scope.status();
+  return stream_step_tiled<InT, kModeFir>(job, so, stream);
 }
 
 }  // namespace gsdr

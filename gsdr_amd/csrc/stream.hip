@@ -24,6 +24,7 @@
 #include "gsdr/gsdr_ext.h"
 #include "gsdr/stream.h"
 #include "launch.hpp"
+#include "stream_step.hpp"
 
 struct gsdrxStream_t {
   int kind = GSDRX_STREAM_FIR;
@@ -48,41 +49,6 @@ struct gsdrxStream_t {
 };
 
 namespace gsdr {
-// fir_int8.hip: gsdrxFirFCInt8 for outputs starting at absolute output index outputIndex
-hipError_t fir_int8_at(uint64_t outputIndex, size_t decimation, const float* taps, size_t tapCount,
-                       const int8_t* input, hipFloatComplex* output, size_t numOutputs, int32_t device,
-                       hipStream_t stream);
-hipError_t fir_int8_stream_step(uint64_t outputIndex, const float* taps, size_t tapCount, const int8_t* chunk,
-                                uint64_t chunkLen, int64_t inOff, const int8_t* hist, uint64_t histLen, int8_t* histOut,
-                                int64_t histFrom, uint64_t histN, hipFloatComplex* output, size_t numOutputs,
-                                int32_t device, hipStream_t stream);
-// the one-launch steps on the tiled kernels (fir_dispatch.hpp stream_step_tiled): fir.hip, fir_int8.hip, fm_am.hip
-hipError_t fir_fc_stream_step(size_t decimation, const float* taps, size_t tapCount, const hipFloatComplex* chunk,
-                              uint64_t chunkLen, int64_t inOff, const hipFloatComplex* hist, uint64_t histLen,
-                              hipFloatComplex* histOut, int64_t histFrom, uint64_t histN, hipFloatComplex* output,
-                              size_t numOutputs, int32_t device, hipStream_t stream);
-hipError_t fir_int8_stream_step_tiled(size_t decimation, const float* taps, size_t tapCount, const int8_t* chunk,
-                                      uint64_t chunkLen, int64_t inOff, const int8_t* hist, uint64_t histLen,
-                                      int8_t* histOut, int64_t histFrom, uint64_t histN, hipFloatComplex* output,
-                                      size_t numOutputs, int32_t device, hipStream_t stream);
-hipError_t chain_stream_step_tiled(int mode, bool int8, float fs, float tune, float chan, float dev, uint32_t decimation,
-                                   size_t firstSampleIndex, const float* taps, size_t tapCount, const void* chunk,
-                                   uint64_t chunkLen, int64_t inOff, const void* hist, uint64_t histLen, void* histOut,
-                                   int64_t histFrom, uint64_t histN, float* output, size_t numOutputs, int32_t device,
-                                   hipStream_t stream);
-hipError_t chain_multi_stream_step(int mode, float fs, float tune, const float* chans, const float* devs, uint32_t count,
-                                   uint32_t decimation, size_t firstSampleIndex, const float* taps, size_t tapCount,
-                                   const hipFloatComplex* chunk, uint64_t chunkLen, int64_t inOff,
-                                   const hipFloatComplex* hist, uint64_t histLen, hipFloatComplex* histOut,
-                                   int64_t histFrom, uint64_t histN, float* output, size_t outStride, size_t numOutputs,
-                                   int32_t device, hipStream_t stream);
-// fm_am.hip (mode 1 = FM, 2 = AM as in fir_engine.hpp)
-hipError_t chain_int8_stream_step(int mode, float fs, float tune, float chan, float dev, size_t firstSampleIndex,
-                                  const float* taps, size_t tapCount, const int8_t* chunk, uint64_t chunkLen,
-                                  int64_t inOff, const int8_t* hist, uint64_t histLen, int8_t* histOut,
-                                  int64_t histFrom, uint64_t histN, float* output, size_t numOutputs, int32_t device,
-                                  hipStream_t stream);
-
 namespace {
 
 struct Plan {
@@ -171,6 +137,26 @@ hipError_t gather(const Gather& g, hipStream_t st) {
   const uint32_t blocks = (uint32_t)std::min<uint64_t>(64, ceil_div<uint64_t>(most, 256u * 4u));
   k_stream_gather<<<blocks, 256, 0, st>>>(g);
   return launch_status();
+}
+
+// One channel's one-launch step: int8 I/Q at decimation 4 on the matrix cores, every other shape on the tiled
+// kernels (the same kernels as one monolithic call, tile for tile). hipErrorNotSupported, with nothing
+// launched: the shape has no one-launch step.
+hipError_t channel_step(const gsdrxStream_t& s, const ChainSpec& cs, size_t c, const StreamOperands& so, void* out,
+                        size_t n, hipStream_t st) {
+  const bool i8 = s.format == GSDRX_SAMPLES_CS8;
+  hipError_t e = hipErrorNotSupported;
+  if (s.kind == GSDRX_STREAM_FIR) {
+    hipFloatComplex* o = static_cast<hipFloatComplex*>(out);
+    if (i8) e = fir_int8_stream_step(s.next_out, s.D, s.taps, s.T, so, o, n, s.device, st);
+    if (e != hipErrorNotSupported) return e;
+    return i8 ? fir_int8_stream_step_tiled(s.D, s.taps, s.T, so, o, n, s.device, st)
+              : fir_fc_stream_step(s.D, s.taps, s.T, so, o, n, s.device, st);
+  }
+  float* o = static_cast<float*>(out);
+  if (i8) e = chain_int8_stream_step(cs, s.chans[c], s.devs[c], so, o, n, s.device, st);
+  if (e != hipErrorNotSupported) return e;
+  return chain_stream_step_tiled(cs, i8, s.chans[c], s.devs[c], so, o, n, s.device, st);
 }
 
 }  // namespace
@@ -301,54 +287,28 @@ GSDR_C_LINKAGE hipError_t gsdrxStreamProcess(gsdrxStream s, const void* input, s
     // before the chunk read from the history buffer), the direct outputs and the next history copy: the int8
     // matrix-core kernels at decimation 4, the tiled kernels otherwise (the same kernels as one monolithic
     // call, tile for tile). Every channel reads the old history; only channel 0's launch writes the next one.
-    const int64_t in_off = (int64_t)(s->next_out * s->D) - (int64_t)S;
-    const int64_t from = (int64_t)(p.m_end * s->D) - (int64_t)S;
-    const bool i8 = s->format == GSDRX_SAMPLES_CS8;
-    const int mode = s->kind == GSDRX_STREAM_FM ? 1 : 2;
+    gsdr::StreamOperands so{};
+    so.chunk = chunk;
+    so.chunk_len = numInputSamples;
+    so.in_off = (int64_t)h0 - (int64_t)S;
+    so.hist = s->hist;
+    so.hist_len = h;
+    so.hist_out = s->spare;
+    so.hist_from = (int64_t)(p.m_end * s->D) - (int64_t)S;
+    so.hist_n = p.hist_after;
+    // (the chain part is unused by a FIR stream)
+    const gsdr::ChainSpec cs{s->kind == GSDRX_STREAM_FM ? gsdr::kModeFm : gsdr::kModeAm, s->fs, s->tune, s->D,
+                             s->n0 + h0, s->taps, s->T};
     e = hipErrorNotSupported;
-    if (C > 1 && !i8) {
-      e = gsdr::chain_multi_stream_step(mode, s->fs, s->tune, s->chans.data(), s->devs.data(), (uint32_t)C, s->D,
-                                        s->n0 + h0, s->taps, s->T, reinterpret_cast<const hipFloatComplex*>(chunk),
-                                        numInputSamples, in_off, reinterpret_cast<const hipFloatComplex*>(s->hist), h,
-                                        reinterpret_cast<hipFloatComplex*>(s->spare), from, p.hist_after,
+    if (C > 1 && s->format != GSDRX_SAMPLES_CS8) {
+      e = gsdr::chain_multi_stream_step(cs, s->chans.data(), s->devs.data(), (uint32_t)C, so,
                                         reinterpret_cast<float*>(out), outputCapacity, n_out, s->device, cudaStream);
     }
     // otherwise one launch per channel; a shape without a one-launch step returns hipErrorNotSupported from
     // channel 0, before anything was launched, and the call takes the seam path below
     for (size_t c = 0; c < C && e == hipErrorNotSupported; ++c) {
-      void* hout = c == 0 ? s->spare : nullptr;
-      char* oc = out + c * ostride;
-      hipError_t ec = hipErrorNotSupported;
-      if (i8 && s->D == 4) {
-        const int8_t* c8 = reinterpret_cast<const int8_t*>(chunk);
-        const int8_t* h8 = reinterpret_cast<const int8_t*>(s->hist);
-        int8_t* n8 = static_cast<int8_t*>(hout);
-        if (s->kind == GSDRX_STREAM_FIR) {
-          ec = gsdr::fir_int8_stream_step(s->next_out, s->taps, s->T, c8, numInputSamples, in_off, h8, h, n8, from,
-                                          p.hist_after, reinterpret_cast<hipFloatComplex*>(oc), n_out, s->device,
-                                          cudaStream);
-        } else {
-          ec = gsdr::chain_int8_stream_step(mode, s->fs, s->tune, s->chans[c], s->devs[c], s->n0 + h0, s->taps, s->T,
-                                            c8, numInputSamples, in_off, h8, h, n8, from, p.hist_after,
-                                            reinterpret_cast<float*>(oc), n_out, s->device, cudaStream);
-        }
-      }
-      if (ec == hipErrorNotSupported) {
-        if (s->kind == GSDRX_STREAM_FIR) {
-          ec = i8 ? gsdr::fir_int8_stream_step_tiled(s->D, s->taps, s->T, reinterpret_cast<const int8_t*>(chunk),
-                                                     numInputSamples, in_off, reinterpret_cast<const int8_t*>(s->hist), h,
-                                                     static_cast<int8_t*>(hout), from, p.hist_after,
-                                                     reinterpret_cast<hipFloatComplex*>(oc), n_out, s->device, cudaStream)
-                  : gsdr::fir_fc_stream_step(s->D, s->taps, s->T, reinterpret_cast<const hipFloatComplex*>(chunk),
-                                             numInputSamples, in_off, reinterpret_cast<const hipFloatComplex*>(s->hist), h,
-                                             static_cast<hipFloatComplex*>(hout), from, p.hist_after,
-                                             reinterpret_cast<hipFloatComplex*>(oc), n_out, s->device, cudaStream);
-        } else {
-          ec = gsdr::chain_stream_step_tiled(mode, i8, s->fs, s->tune, s->chans[c], s->devs[c], s->D, s->n0 + h0,
-                                             s->taps, s->T, chunk, numInputSamples, in_off, s->hist, h, hout, from,
-                                             p.hist_after, reinterpret_cast<float*>(oc), n_out, s->device, cudaStream);
-        }
-      }
+      const hipError_t ec = gsdr::channel_step(*s, cs, c, so, out + c * ostride, n_out, cudaStream);
+      so.hist_out = nullptr;  // the channels after the first only read the old history
       if (ec == hipErrorNotSupported && c == 0) break;
       // a failure after channel 0 leaves channels 0..c-1 written and the stream unchanged (stream.h: the
       // outputs of a failed call are unspecified)

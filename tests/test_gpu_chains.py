@@ -85,6 +85,53 @@ def test_fm_streaming_chunks_equal_monolithic(cuda, D):
     assert torch.equal(torch.cat(parts), whole)
 
 
+@pytest.mark.parametrize("D", [2, 4])
+@pytest.mark.parametrize("kind", ["fm", "am"])
+def test_chain_split_straddles_2_pow_32_outputs(cuda, kind, D):
+    """The split-invariance contract where the absolute output index firstSampleIndex / D crosses 2^32: the
+    anchored tiles' NCO cell grid is q0 mod the tile stride, and the FM strides (255 / 510 / 1020
+    at D = 4, 1016 at D = 2) do not divide 2^32, so q0 has to be carried in 64 bits. Chunks on both sides of the
+    boundary (the second ends exactly at output 2^32) reproduce one call bit for bit; a call wholly above the
+    boundary meets the oracle and its own two-chunk split."""
+    from gsdr_amd import ops
+    from gsdr_amd.signals import fm_test_signal, lowpass_taps, uniform_iq
+
+    T, N = 31, 4096
+    fm = kind == "fm"
+    L = (N if fm else N - 1) * D + T
+    x_np = fm_test_signal(L, fs=FS, seed=D) if fm else (0.7 * uniform_iq(L, seed=D)).astype(np.complex64)
+    taps_np = lowpass_taps(T, 0.1)
+    x, taps = dev(x_np, cuda), dev(taps_np, cuda)
+
+    def call(xs, n0, n):
+        if fm:
+            return ops.fm_demod(xs, taps, FS, TUNE, CHAN, DEV, D, n0, n)
+        return ops.am_demod(xs, taps, FS, TUNE, CHAN, D, n0, n)
+
+    def chunked(n0, sizes):
+        parts, m = [], 0
+        for n in sizes:
+            parts.append(call(x[m * D:(m + (n if fm else n - 1)) * D + T], n0 + m * D, n))
+            m += n
+        assert m == N
+        return torch.cat(parts)
+
+    n0 = D * ((1 << 32) - 2048) + 1
+    whole = call(x, n0, N)
+    assert torch.equal(chunked(n0, (1000, 1048, 1, 2047)), whole)
+
+    n0 = D * ((1 << 32) + 777)
+    above = call(x, n0, N)
+    torch.cuda.synchronize()
+    if fm:
+        ref = o.fm_demod(x_np, taps_np, FS, TUNE, CHAN, DEV, D, n0, N)
+        assert wrapped_angle_err(above.cpu().numpy(), ref, fm_gain()) <= FLOAT_TOL
+    else:
+        ref = o.am_demod(x_np, taps_np, FS, TUNE, CHAN, D, n0, N)
+        assert float(np.max(np.abs(above.cpu().numpy() - ref))) <= FLOAT_TOL
+    assert torch.equal(chunked(n0, (1500, N - 1500)), above)
+
+
 def test_fm_pure_tone_known_answer(cuda):
     """A noiseless FM carrier at a constant offset f from the channel discriminates to the constant
     g * 2 pi f D'/fs where the discriminator sees decimated samples: arg step = 2 pi f D / fs."""

@@ -101,6 +101,50 @@ def test_one_launch_calls_equal_monolithic(cuda, kind, D, T, L, nchunks):
     assert torch.equal(got.view(torch.float32), want.view(torch.float32))
 
 
+@pytest.mark.parametrize("D,int8", [(2, False), (4, False), (2, True)])
+def test_fm_stream_straddles_2_pow_32_outputs(cuda, D, int8):
+    """The absolute output index firstSampleIndex / D crosses 2^32 at the stream's output 2048: the FM tiles' NCO
+    cell grid is that index modulo a stride that does not divide 2^32, so every call, below,
+    across and above the boundary, must still reproduce the monolithic call bit for bit. (int8 at D = 2 runs the
+    float-shaped tiles.)"""
+    from gsdr_amd.signals import fm_test_signal, lowpass_taps
+    from gsdr_amd.stream import Stream
+
+    T, cap = 31, 700  # short chunks: dozens of calls on each side of the boundary
+    W = T + D
+    n0 = D * ((1 << 32) - 2048) + 1
+    L = 4096 * D + W
+    x = fm_test_signal(L, noise=0.02, n0=12345)
+    if int8:
+        xh = np.clip(np.round(np.stack([x.real, x.imag], 1).ravel() * 100), -128, 127).astype(np.int8)
+        per = 2
+    else:
+        xh, per = x, 1
+    xd = torch.from_numpy(xh).to(cuda)
+    taps = torch.from_numpy(lowpass_taps(T)).to(cuda)
+    want = monolithic("fm", xd, taps, D, n0, int8)
+    sizes, left = [], L
+    for m in chunks(64 * L, seed=D * 10 + int8, W=W):
+        sizes.append(min(m, cap, left))
+        left -= sizes[-1]
+        if left == 0:
+            break
+    ends = np.cumsum(sizes)
+    assert left == 0 and max(sizes) <= 3000
+    assert sum(1 for e, m in zip(ends, sizes) if m and e <= 2048 * D) >= 3      # calls wholly below the boundary
+    assert sum(1 for e, m in zip(ends, sizes) if m and e - m >= 2048 * D + W) >= 3  # and wholly above it
+    s = Stream("fm", taps, D, FS, TUNE, CHAN, DEV, first_sample_index=n0, int8=int8)
+    parts, pos = [], 0
+    for m in sizes:
+        parts.append(s.process(xd[pos * per:(pos + m) * per]).clone())
+        pos += m
+    s.close()
+    got = torch.cat(parts)
+    torch.cuda.synchronize()
+    assert got.numel() == want.numel() == 4097
+    assert torch.equal(got.view(torch.float32), want.view(torch.float32))
+
+
 def test_tiny_chunks_and_skipping_decimation(cuda):
     """D > W: outputs skip samples; one-sample chunks throughout."""
     from gsdr_amd import ops
