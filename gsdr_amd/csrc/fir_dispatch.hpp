@@ -39,7 +39,7 @@ struct FirJob {
   float fm_gain = 0.0f;
   uint32_t out_phase = 0;  // absolute index of output 0 mod 16 (fir_i8_mfma.hpp)
   uint64_t q0 = 0;         // chains: absolute index of output 0 (firstSampleIndex / D) -- the anchored
-                           // polyphase tiles' NCO cell grid (fir_engine.hpp, stage_tile_rel)
+                           // polyphase tiles' NCO cell grid (fir_engine.hpp, MixAnchored)
   // a streaming step's operands (FirParams): `in` is then the chunk and L its length. All zero otherwise.
   StreamOperands step{};
   // the streaming object's one-launch path on the tiled kernels (stream_step_tiled): only the polyphase and
@@ -170,7 +170,7 @@ hipError_t launch_generic(const FirJob& j, hipStream_t s) {
 }
 
 // Tile grid of the polyphase kernels. FIR: tile t = outputs [t KT, (t + 1) KT). FM / AM chains (anchored NCO,
-// fir_engine.hpp stage_tile_rel): tiles on an absolute output grid of stride S -- KT for AM; KT - R for FM, whose
+// fir_engine.hpp MixAnchored): tiles on an absolute output grid of stride S -- KT for AM; KT - R for FM, whose
 // tiles overlap by one thread's outputs so that every discriminator pairs two outputs of one tile -- output 0
 // (absolute index q0) sits at tile_shift = q0 mod S in tile 0, which is sub-tile cell_sub0 of its NCO cell of
 // SUBS tiles (CELL = SUBS S outputs; the short-call shapes of a decimation are sub-tiles of its largest tile, whose

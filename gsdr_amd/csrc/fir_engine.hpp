@@ -375,16 +375,14 @@ constexpr int staging_batch(int bpt) {
   return 1;
 }
 
-// Stage granules [0, NG) of the tile starting at global sample S0 into LDS (padded layout).
-// The first SG*WG granules (the tile body) are loaded fully unrolled so every HBM load is in flight
-// before the first LDS write; the remaining halo granules follow in a short strided loop.
 // Tile body by LDS-DMA (global_load_lds_dwordx4: HBM -> LDS with no VGPR round trip and no ds_write).
 // One wave instruction fills 64 consecutive LDS slots; the padded layout is kept by choosing each
 // lane's SOURCE granule (slot s holds granule s - s / SGP of its segment; pad slots are skipped with
-// the lane masked off). Returns false when the tile does not qualify (then nothing was issued).
-template <class InT, class Geo, int WG, int MODE, bool NT>
+// the lane masked off). Returns false when the tile does not qualify (then nothing was issued): only unmixed
+// complex samples do (MIXED: the tile has an NCO mixer).
+template <class InT, class Geo, int WG, bool MIXED, bool NT>
 __device__ __forceinline__ bool stage_body_dma(float4* __restrict__ lds, const InT* __restrict__ in, uint64_t S0) {
-  if constexpr (!std::is_same<InT, float2>::value || MODE != kModeFir) {
+  if constexpr (!std::is_same<InT, float2>::value || MIXED) {
     return false;
   } else {
     constexpr int BODY = Geo::SG * (Geo::KT / Geo::ROUT);  // body granules
@@ -405,64 +403,6 @@ __device__ __forceinline__ bool stage_body_dma(float4* __restrict__ lds, const I
       }
     }
     return true;
-  }
-}
-
-// Streaming one-launch path (FirParams::hist != nullptr): local sample s of the tiled kernels (counted
-// from output 0's window start, `in` = chunk + in_off) is chunk sample s + in_off; the ones before the
-// chunk come from the history. Samples at or past L read as zero.
-template <class InT>
-__device__ __forceinline__ typename LdsSample<InT>::type stream_sample(const InT* __restrict__ in,
-                                                                        const FirParams& p, uint64_t s) {
-  using LdsT = typename LdsSample<InT>::type;
-  if (s >= p.L) {
-    LdsT z;
-    set_zero(z);
-    return z;
-  }
-  const int64_t i = (int64_t)s + p.in_off;
-  return i < 0 ? to_lds_sample(reinterpret_cast<const InT*>(p.hist)[(int64_t)p.hist_len + i]) : to_lds_sample(in[s]);
-}
-
-// A tile that reaches into the stream's history (only the first tile of a call: the history is shorter
-// than one window): sample by sample, each from the history or the chunk (stream_sample's rule), in batches of
-// 8 granules a thread whose loads are all issued before the first is used (one granule at a time, this tile
-// had waited on every load in turn and ran ~1 us longer than the call's other tiles).
-template <class InT, class Geo, int WG, int MODE>
-__device__ __forceinline__ void stage_tile_stream(float4* __restrict__ lds, const InT* __restrict__ in, uint64_t S0,
-                                                  uint32_t NG, const FirParams& p) {
-  constexpr int G = Geo::G;
-  constexpr int B = 8;
-  const InT* __restrict__ hist = reinterpret_cast<const InT*>(p.hist);
-  for (uint32_t g0 = 0; g0 < NG; g0 += B * WG) {
-    InT v[B][G];
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-      const uint32_t g = g0 + (uint32_t)b * WG + threadIdx.x;
-#pragma unroll
-      for (int e = 0; e < G; ++e) {
-        const uint64_t s = S0 + (uint64_t)g * G + (uint64_t)e;
-        const int64_t i = (int64_t)s + p.in_off;
-        if (g < NG && s < p.L) {
-          v[b][e] = i < 0 ? hist[(int64_t)p.hist_len + i] : in[s];
-        } else {
-          set_zero(v[b][e]);
-        }
-      }
-    }
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-      const uint32_t g = g0 + (uint32_t)b * WG + threadIdx.x;
-      if (g >= NG) break;
-      float4 w;
-      if constexpr (G == 2) {
-        const float2 a = to_lds_sample(v[b][0]), c = to_lds_sample(v[b][1]);
-        w = make_float4(a.x, a.y, c.x, c.y);
-      } else {
-        w = make_float4(v[b][0], v[b][1], v[b][2], v[b][3]);
-      }
-      lds[Geo::padded(g)] = stage_transform<InT, MODE>(w, (uint32_t)(S0 + (uint64_t)g * G), p);
-    }
   }
 }
 
@@ -544,190 +484,94 @@ struct HaloPre {
   }
 };
 
-// SH (complex or int8 I/Q samples): the input is one sample off its aligned granule load (complex: 8 bytes
-// off 16; int8 I/Q: 2 bytes off 4) at every tile start. The tile
-// body is then loaded as aligned 16-byte granules starting one sample early, and each loaded pair is
-// split over two LDS granules (second half of slot g - 1, first half of slot g); the halo re-writes the
-// body's last slot whole. The NCO phasor is a function of the absolute index, so the odd-start pairs
-// mix exactly as the even-start ones would.
-template <class InT, class Geo, int WG, bool VEC, int MODE, bool NT = false, bool DMA = false, int SH = 0>
-__device__ __forceinline__ void stage_tile(float4* __restrict__ lds, const InT* __restrict__ in, uint64_t S0,
-                                           uint32_t NG, const FirParams& p) {
-  constexpr int G = Geo::G;
-  if (p.hist != nullptr && (int64_t)S0 + p.in_off < 0) {  // uniform: the tile starts in the stream's history
-    stage_tile_stream<InT, Geo, WG, MODE>(lds, in, S0, NG, p);
-    return;
-  }
-  // tile body granules per staging thread (Geo::KT / R output segments of SG granules over WG threads)
-  constexpr int BPT = Geo::SG * (Geo::KT / Geo::ROUT) / WG;
-  static_assert(BPT * WG == Geo::SG * (Geo::KT / Geo::ROUT), "tile body must split evenly over the threads");
-  // at most 8 granules (128 B) in flight per lane: bounds the staging registers for large segments
-  constexpr int SB = staging_batch(BPT);
-  static_assert(BPT % SB == 0, "segment granules must split into whole staging batches");
-  const uint32_t tid = threadIdx.x;
-  const PhaseWalk pw = phase_walk<G, WG>(p.nco_n0, S0, p.nco_inc);
-  // wave-uniform: is the whole staged span readable? (every tile but the last)
-  const bool whole = VEC && (int64_t)S0 >= 0 && (S0 + (uint64_t)NG * G <= p.L);
-  if constexpr (SH != 0 && std::is_same<InT, float>::value) {
-    // real samples SH (1..3) floats off 16-byte alignment (4-byte aligned): aligned 16-byte loads from
-    // SH samples early; loaded quad g holds the last SH samples of granule g - 1 and the first 4 - SH of
-    // granule g, written as two partial-granule LDS stores (8-byte aligned pieces). The halo re-writes
-    // the body's last granule whole, as for complex input.
-    static_assert(!VEC && SH > 0 && SH < 4, "shifted real staging: 1..3 floats off 16-byte alignment");
-    // (a tile less than SH samples past the start of the caller's buffer would load samples before it --
-    // inside its first 16-byte block, so it cannot fault, but it is out of bounds: that tile takes the
-    // per-granule loads below instead. The buffer starts at `in - in_off` on the streaming path.)
-    if ((int64_t)S0 + p.in_off >= (int64_t)SH && S0 + (uint64_t)NG * G <= p.L) {
-      float* __restrict__ l1 = reinterpret_cast<float*>(lds);
-      const float4* __restrict__ src = reinterpret_cast<const float4*>(in + S0 - SH);  // 16-byte aligned
+// One staging batch: SB granules WG apart from granule g0 of an aligned base (int8 I/Q words or 16-byte quads, plain
+// or non-temporal), all loaded before the first is converted.
+template <class InT, int SB, int WG, bool NT>
+__device__ __forceinline__ void load_batch(float4 (&v)[SB], const InT* __restrict__ base, uint32_t g0) {
+  if constexpr (std::is_same<InT, Iq8>::value) {
+    const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(base);
+    uint32_t w[SB];
 #pragma unroll
-      for (int b0 = 0; b0 < BPT; b0 += SB) {
-        float4 v[SB];
+    for (int k = 0; k < SB; ++k) w[k] = NT ? __builtin_nontemporal_load(src + g0 + k * WG) : src[g0 + k * WG];
 #pragma unroll
-        for (int k = 0; k < SB; ++k) v[k] = NT ? load16_nt(src + (b0 + k) * WG + tid) : src[(b0 + k) * WG + tid];
-#pragma unroll
-        for (int k = 0; k < SB; ++k) {
-          const uint32_t g = (b0 + k) * WG + tid;
-          float* __restrict__ lo = l1 + 4 * Geo::padded(g);  // granule g
-          if constexpr (SH == 2) {
-            if (g > 0) *reinterpret_cast<float2*>(l1 + 4 * Geo::padded(g - 1) + 2) = make_float2(v[k].x, v[k].y);
-            *reinterpret_cast<float2*>(lo) = make_float2(v[k].z, v[k].w);
-          } else if constexpr (SH == 1) {
-            if (g > 0) l1[4 * Geo::padded(g - 1) + 3] = v[k].x;
-            *reinterpret_cast<float2*>(lo) = make_float2(v[k].y, v[k].z);
-            lo[2] = v[k].w;
-          } else {
-            if (g > 0) {
-              float* __restrict__ pv = l1 + 4 * Geo::padded(g - 1);
-              pv[1] = v[k].x;
-              *reinterpret_cast<float2*>(pv + 2) = make_float2(v[k].y, v[k].z);
-            }
-            lo[0] = v[k].w;
-          }
-        }
-      }
-      for (uint32_t g = BPT * WG - 1 + tid; g < NG; g += WG) {
-        const uint64_t s = S0 + (uint64_t)g * G;
-        lds[Geo::padded(g)] = load_granule<InT, false>(in, s, p.L);
-      }
-      return;
-    }
-  } else if constexpr (SH != 0) {
-    static_assert((std::is_same<InT, float2>::value || std::is_same<InT, Iq8>::value) && !VEC && SH == 1,
-                  "shifted staging is for 8-byte-aligned complex or 2-byte-aligned int8 I/Q input");
-    // (a tile starting at the caller's buffer, chunk = in - in_off, would load the sample before it)
-    if ((int64_t)S0 + p.in_off >= 1 && S0 + (uint64_t)NG * G <= p.L) {
-      float2* __restrict__ l2 = reinterpret_cast<float2*>(lds);
-#pragma unroll
-      for (int b0 = 0; b0 < BPT; b0 += SB) {
-        float4 v[SB];
-        if constexpr (std::is_same<InT, Iq8>::value) {
-          const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(in + S0 - 1);  // 4-byte aligned
-          uint32_t w[SB];
-#pragma unroll
-          for (int k = 0; k < SB; ++k) {
-            w[k] = NT ? __builtin_nontemporal_load(src + (b0 + k) * WG + tid) : src[(b0 + k) * WG + tid];
-          }
-#pragma unroll
-          for (int k = 0; k < SB; ++k) v[k] = iq8x2_granule(w[k]);
-        } else {
-          const float4* __restrict__ src = reinterpret_cast<const float4*>(in + S0 - 1);  // 16-byte aligned
-#pragma unroll
-          for (int k = 0; k < SB; ++k) {
-            if constexpr (NT) {
-              v[k] = load16_nt(src + (b0 + k) * WG + tid);
-            } else {
-              v[k] = src[(b0 + k) * WG + tid];
-            }
-          }
-        }
-#pragma unroll
-        for (int k = 0; k < SB; ++k) {
-          const uint32_t g = (b0 + k) * WG + tid;
-          // samples S0 + 2g - 1 (odd start relative to the tile) and S0 + 2g
-          const float4 w = stage_transform_ph<InT, MODE>(v[k], pw.ph0 + (uint32_t)(b0 + k) * pw.step - pw.inc, !pw.odd,
-                                                         pw.inc);
-          if (g > 0) l2[2 * Geo::padded(g - 1) + 1] = make_float2(w.x, w.y);
-          l2[2 * Geo::padded(g)] = make_float2(w.z, w.w);
-        }
-      }
-      for (uint32_t g = BPT * WG - 1 + tid; g < NG; g += WG) {
-        const uint64_t s = S0 + (uint64_t)g * G;
-        lds[Geo::padded(g)] = stage_transform<InT, MODE>(load_granule<InT, false>(in, s, p.L), (uint32_t)s, p);
-      }
-      return;
-    }
-  }
-  if constexpr (DMA) {
-    if (whole && stage_body_dma<InT, Geo, WG, MODE, NT>(lds, in, S0)) {
-      for (uint32_t g = BPT * WG + tid; g < NG; g += WG) {
-        const uint64_t s = S0 + (uint64_t)g * G;
-        lds[Geo::padded(g)] = stage_transform<InT, MODE>(load_granule<InT, VEC>(in, s, p.L), (uint32_t)s, p);
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      return;
-    }
-  }
-  HaloPre<InT, VEC> halo(S0, BPT * WG + tid, NG, p.L);
-  // The body loop, instantiated once per NCO start parity (`odd` is uniform over the tile): with the
-  // parity a runtime value the compiler kept a branch around every granule's phasor.
-  const uint32_t pbase = Geo::padded(tid);
-  auto body = [&](auto odd_c) {
-    constexpr bool ODD = decltype(odd_c)::value;
-#pragma unroll
-  for (int b0 = 0; b0 < BPT; b0 += SB) {
-    float4 v[SB];
-    if (whole) {
-      if constexpr (std::is_same<InT, Iq8>::value) {
-        const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(in + S0);
-        uint32_t w[SB];
-#pragma unroll
-        for (int k = 0; k < SB; ++k) {
-          w[k] = NT ? __builtin_nontemporal_load(src + (b0 + k) * WG + tid) : src[(b0 + k) * WG + tid];
-        }
-#pragma unroll
-        for (int k = 0; k < SB; ++k) v[k] = iq8x2_granule(w[k]);
-      } else {
-        const float4* __restrict__ src = reinterpret_cast<const float4*>(in + S0);
-#pragma unroll
-        for (int k = 0; k < SB; ++k) {
-          if constexpr (NT) {
-            v[k] = load16_nt(src + (b0 + k) * WG + tid);
-          } else {
-            v[k] = src[(b0 + k) * WG + tid];
-          }
-        }
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < SB; ++k) {
-        v[k] = load_granule<InT, VEC>(in, S0 + (uint64_t)((b0 + k) * WG + tid) * G, p.L);
-      }
-    }
-    if (b0 == 0) halo.issue(in);
+    for (int k = 0; k < SB; ++k) v[k] = iq8x2_granule(w[k]);
+  } else {
+    const float4* __restrict__ src = reinterpret_cast<const float4*>(base);
 #pragma unroll
     for (int k = 0; k < SB; ++k) {
-      const uint32_t g = (b0 + k) * WG + tid;
-      // padded(k * WG + tid) = padded(tid) + k * padded(WG) when whole segments fit a workgroup's row of
-      // granules: a per-thread base plus an immediate offset per granule
-      const uint32_t slot = (WG % Geo::SG == 0) ? pbase + (uint32_t)(b0 + k) * Geo::padded(WG) : Geo::padded(g);
-      lds[slot] = stage_transform_ph<InT, MODE>(v[k], pw.ph0 + (uint32_t)(b0 + k) * pw.step, ODD, pw.inc);
+      if constexpr (NT) {
+        v[k] = load16_nt(src + g0 + k * WG);
+      } else {
+        v[k] = src[g0 + k * WG];
+      }
     }
   }
-  };
-  if constexpr (MODE == kModeFir) {
-    body(std::false_type{});
-  } else if (pw.odd) {
-    body(std::true_type{});
-  } else {
-    body(std::false_type{});
-  }
-  if (halo.g < NG) lds[Geo::padded(halo.g)] = stage_transform<InT, MODE>(halo.get(in, p.L), (uint32_t)halo.s, p);
-  for (uint32_t g = halo.g + WG; g < NG; g += WG) {
-    const uint64_t s = S0 + (uint64_t)g * G;
-    lds[Geo::padded(g)] = stage_transform<InT, MODE>(load_granule<InT, VEC>(in, s, p.L), (uint32_t)s, p);
-  }
 }
+
+// ------------------------------------------------------------------------------------------------
+// Staging mixers: what stage_tile does to a granule between its load and its LDS store. A thread's tile granules
+// are g = k WG + tid, row k = 0, 1, ...; stage_tile hands each of them to its mixer once, in ascending row order:
+//   row(v, k, odd)     granule of body row k (k and the NCO start parity `odd`, see per_parity, are compile-time
+//                      constants after unrolling);
+//   shifted_row(v, k, prev)  body row k of the shifted path: the loaded pair (sample 2g - 1, sample 2g); `prev`,
+//                      from begin_shifted(), is what the mixer keeps for sample 2g - 1 and lives in that path only;
+//   next(v, s, advance)  the thread's next granule (the halo; every granule of a history tile, whose first row
+//                      passes advance = false); s = the local index of its first sample. After shifted_halo(prev)
+//                      these granules are those one granule before the rows' pairs (g = k WG + tid - 1).
+// A mixer holds phasor state only. Every path must form the same phasor for the same sample: that is what makes any
+// split of a stream into calls bit-identical.
+// ------------------------------------------------------------------------------------------------
+// FIR mode (and the probes' staging without the mix): the identity
+struct MixNone {
+  template <class F>
+  __device__ __forceinline__ void per_parity(F&& body) {
+    body(std::false_type{});
+  }
+  template <class ODD>
+  __device__ __forceinline__ float4 row(float4 v, int, ODD) {
+    return v;
+  }
+  struct Prev {};
+  __device__ __forceinline__ Prev begin_shifted() { return {}; }
+  __device__ __forceinline__ float4 shifted_row(float4 v, int, Prev&) { return v; }
+  __device__ __forceinline__ void shifted_halo(const Prev&) {}
+  __device__ __forceinline__ float4 next(float4 v, uint64_t, bool = true) { return v; }
+};
+
+// The absolute phasor (k_fir_contig's chains): a pure function of the absolute sample index, so any way of arriving
+// at the same integer phase gives the same bits. The body rows walk the phase (PhaseWalk); the rest multiply.
+template <class InT, int MODE, int WG>
+struct MixAbsolute {
+  const FirParams& p;
+  PhaseWalk pw;
+  __device__ __forceinline__ MixAbsolute(const FirParams& p_, uint64_t S0)
+      : p(p_), pw(phase_walk<SampleT<InT>::kPerGranule, WG>(p_.nco_n0, S0, p_.nco_inc)) {}
+  // The body loop is instantiated once per NCO start parity (`odd` is uniform over the tile): with the parity a
+  // runtime value the compiler kept a branch around every granule's phasor.
+  template <class F>
+  __device__ __forceinline__ void per_parity(F&& body) {
+    if (pw.odd) {
+      body(std::true_type{});
+    } else {
+      body(std::false_type{});
+    }
+  }
+  template <class ODD>
+  __device__ __forceinline__ float4 row(float4 v, int k, ODD) {
+    return stage_transform_ph<InT, MODE>(v, pw.ph0 + (uint32_t)k * pw.step, ODD::value, pw.inc);
+  }
+  struct Prev {};
+  __device__ __forceinline__ Prev begin_shifted() { return {}; }
+  // samples S0 + 2g - 1 (odd start relative to the tile) and S0 + 2g: the odd-start pairs mix exactly as the
+  // even-start ones would
+  __device__ __forceinline__ float4 shifted_row(float4 v, int k, Prev&) {
+    return stage_transform_ph<InT, MODE>(v, pw.ph0 + (uint32_t)k * pw.step - pw.inc, !pw.odd, pw.inc);
+  }
+  __device__ __forceinline__ void shifted_halo(const Prev&) {}
+  __device__ __forceinline__ float4 next(float4 v, uint64_t s, bool = true) {
+    return stage_transform<InT, MODE>(v, (uint32_t)s, p);
+  }
+};
 
 // ------------------------------------------------------------------------------------------------
 // Anchored NCO (the polyphase kernels in FM / AM mode). The FM discriminator and the AM envelope are
@@ -761,154 +605,237 @@ __device__ __forceinline__ float4 rel_mix(float4 v, float2 e, float2 w) {
   return make_float4(a.x, a.y, b.x, b.y);
 }
 
-// stage_tile for an anchored chain. The tile starts row0 WG - sh granules into its cell (0 <= sh < WG): tile granule
-// g = k WG + tid (the staging map of stage_tile) is cell granule (row0 + k) WG + tid - sh, i.e. lane
-// l = (tid - sh) mod WG of cell row r + k with r = row0, or row0 - 1 for tid < sh. So a thread walks lane l's chain
-// from row r, one multiply a row.
-template <class InT, class Geo, int WG, bool VEC, bool NT, int SH>
-__device__ __forceinline__ void stage_tile_rel(float4* __restrict__ lds, const InT* __restrict__ in, uint64_t S0,
-                                               uint32_t NG, const FirParams& p, uint32_t row0, uint32_t sh) {
+// The tile starts row0 WG - sh granules into its cell (0 <= sh < WG): tile granule g = k WG + tid (the staging map
+// of stage_tile) is cell granule (row0 + k) WG + tid - sh, i.e. lane l = (tid - sh) mod WG of cell row r + k with
+// r = row0, or row0 - 1 for tid < sh. So a thread walks lane l's chain from row r, one multiply a row, made when the
+// row is mixed (none for the tile's first row). The sequence of multiplies per (lane, row) is the contract.
+template <int WG>
+struct MixAnchored {
+  uint32_t inc, lane, crow;  // the chain: cell lane, and the cell row of tile row 0
+  float2 w, F, e;
+  __device__ __forceinline__ MixAnchored(uint32_t inc_, uint32_t row0, uint32_t sh)
+      : inc(inc_), lane((threadIdx.x + WG - sh) % WG), crow(row0 - (threadIdx.x < sh ? 1u : 0u)) {
+    w = nco_direct(inc);
+    F = nco_direct((uint32_t)(2 * WG) * inc);
+    e = rel_chain_start<WG>(lane, crow, inc);
+  }
+  template <class F_>
+  __device__ __forceinline__ void per_parity(F_&& body) {
+    body(std::false_type{});
+  }
+  __device__ __forceinline__ float4 next(float4 v, uint64_t, bool advance = true) {
+    if (advance) e = cmul(e, F);
+    return rel_mix(v, e, w);
+  }
+  template <class ODD>
+  __device__ __forceinline__ float4 row(float4 v, int k, ODD) {
+    return next(v, 0, k > 0);
+  }
+  // loaded pair g holds samples 2g - 1 (the odd half of granule g - 1: lane l - 1's chain, or for lane 0
+  // lane WG - 1's chain one row behind) and 2g (granule g): the previous lane's chain `ep` runs beside this one
+  struct Prev {
+    float2 ep;
+    bool lag;  // lane 0 of a cell's first row has no previous granule in the cell
+  };
+  __device__ __forceinline__ Prev begin_shifted() {
+    const uint32_t lp = (lane + WG - 1) % WG;
+    Prev q{nco_direct((2u * lp) * inc), lane == 0 && crow == 0};
+    for (uint32_t i = 0; i < crow; ++i) {
+      const float2 t = cmul(q.ep, F);
+      q.ep = (lane == 0 && i == 0) ? q.ep : t;  // lane 0 follows lane WG - 1 one row behind
+    }
+    return q;
+  }
+  __device__ __forceinline__ float4 shifted_row(float4 v, int k, Prev& q) {
+    if (k > 0) {
+      e = cmul(e, F);
+      const float2 t = cmul(q.ep, F);
+      q.ep = (k == 1 && q.lag) ? q.ep : t;
+    }
+    const float2 a = cmul(make_float2(v.x, v.y), cmul(q.ep, w));  // sample 2g - 1
+    const float2 b = cmul(make_float2(v.z, v.w), e);            // sample 2g
+    return make_float4(a.x, a.y, b.x, b.y);
+  }
+  // the shifted halo's granule g is lane l - 1's (lane 0: lane WG - 1's, one row back), i.e. the previous-lane
+  // chain's
+  __device__ __forceinline__ void shifted_halo(const Prev& q) { e = q.ep; }
+};
+
+// A streaming call's first tile, which reaches into the stream's history (only that tile: the history is shorter
+// than one window). Local sample s (counted from output 0's window start, `in` = chunk + in_off) is chunk sample
+// s + in_off; the ones before the chunk come from the history, samples at or past L read as zero. Sample by sample,
+// in batches of 8 granules a thread whose loads are all issued before the first is used (one granule at a time, this
+// tile had waited on every load in turn and ran ~1 us longer than the call's other tiles).
+template <class InT, class Geo, int WG, class Mix>
+__device__ __forceinline__ void stage_history(float4* __restrict__ lds, const InT* __restrict__ in, uint64_t S0,
+                                              uint32_t NG, const FirParams& p, Mix& m) {
   constexpr int G = Geo::G;
-  static_assert(G == 2, "NCO modes take complex samples");
-  constexpr int BPT = Geo::SG * (Geo::KT / Geo::ROUT) / WG;  // body rows
-  static_assert(BPT * WG == Geo::SG * (Geo::KT / Geo::ROUT), "tile body must split evenly over the threads");
-  constexpr int SB = staging_batch(BPT);
   const uint32_t tid = threadIdx.x;
-  const uint32_t lane = (tid + WG - sh) % WG, row = row0 - (tid < sh ? 1u : 0u);
-  const float2 w = nco_direct(p.nco_inc), F = nco_direct((uint32_t)(2 * WG) * p.nco_inc);
-  float2 e = rel_chain_start<WG>(lane, row, p.nco_inc);
-  if (p.hist != nullptr && (int64_t)S0 + p.in_off < 0) {
-    // a streaming call's first tile, which reaches into the stream's history: sample by sample (stream_sample's
-    // rule; samples before the call's first window read as zero), 8 rows of loads in flight
-    constexpr int B = 8;
-    const InT* __restrict__ hist = reinterpret_cast<const InT*>(p.hist);
-    for (uint32_t g0 = 0; g0 < NG; g0 += B * WG) {
-      InT v[B][G];
+  constexpr int B = 8;
+  const InT* __restrict__ hist = reinterpret_cast<const InT*>(p.hist);
+  for (uint32_t g0 = 0; g0 < NG; g0 += B * WG) {
+    InT v[B][G];
 #pragma unroll
-      for (int b = 0; b < B; ++b) {
-        const uint32_t g = g0 + (uint32_t)b * WG + tid;
+    for (int b = 0; b < B; ++b) {
+      const uint32_t g = g0 + (uint32_t)b * WG + tid;
 #pragma unroll
-        for (int c = 0; c < G; ++c) {
-          const uint64_t s = S0 + (uint64_t)g * G + (uint64_t)c;
-          const int64_t i = (int64_t)s + p.in_off;
-          if (g < NG && s < p.L) {
-            v[b][c] = i < 0 ? hist[(int64_t)p.hist_len + i] : in[s];
+      for (int c = 0; c < G; ++c) {
+        const uint64_t s = S0 + (uint64_t)g * G + (uint64_t)c;
+        const int64_t i = (int64_t)s + p.in_off;
+        if (g < NG && s < p.L) {
+          v[b][c] = i < 0 ? hist[(int64_t)p.hist_len + i] : in[s];
+        } else {
+          set_zero(v[b][c]);
+        }
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < B; ++b) {
+      const uint32_t g = g0 + (uint32_t)b * WG + tid;
+      if (g >= NG) break;
+      float4 w;
+      if constexpr (G == 2) {
+        const float2 a = to_lds_sample(v[b][0]), c = to_lds_sample(v[b][1]);
+        w = make_float4(a.x, a.y, c.x, c.y);
+      } else {
+        w = make_float4(v[b][0], v[b][1], v[b][2], v[b][3]);
+      }
+      lds[Geo::padded(g)] = m.next(w, S0 + (uint64_t)g * G, g0 + (uint32_t)b * WG > 0);
+    }
+  }
+}
+
+// Stage granules [0, NG) of the tile starting at global sample S0 into LDS (padded layout), each mixed by `m` on
+// the way in. The first SG*WG granules (the tile body) are loaded fully unrolled so every HBM load is in flight
+// before the first LDS write; the remaining halo granules follow in a short strided loop.
+// SH (complex or int8 I/Q samples): the input is one sample off its aligned granule load (complex: 8 bytes
+// off 16; int8 I/Q: 2 bytes off 4) at every tile start. The tile body is then loaded as aligned 16-byte granules
+// starting one sample early, and each loaded pair is split over two LDS granules (second half of slot g - 1, first
+// half of slot g); the halo re-writes the body's last slot whole.
+template <class InT, class Geo, int WG, bool VEC, bool NT = false, bool DMA = false, int SH = 0, class Mix>
+__device__ __forceinline__ void stage_tile(float4* __restrict__ lds, const InT* __restrict__ in, uint64_t S0,
+                                           uint32_t NG, const FirParams& p, Mix m) {
+  constexpr int G = Geo::G;
+  constexpr bool MIXED = !std::is_same<Mix, MixNone>::value;
+  static_assert(!MIXED || G == 2, "NCO modes take complex samples");
+  // tile body granules per staging thread (Geo::KT / R output segments of SG granules over WG threads)
+  constexpr int BPT = Geo::SG * (Geo::KT / Geo::ROUT) / WG;
+  static_assert(BPT * WG == Geo::SG * (Geo::KT / Geo::ROUT), "tile body must split evenly over the threads");
+  // at most 8 granules (128 B) in flight per lane: bounds the staging registers for large segments
+  constexpr int SB = staging_batch(BPT);
+  static_assert(BPT % SB == 0, "segment granules must split into whole staging batches");
+  // the halo from tile granule g on, a granule at a time
+  auto stage_halo = [&](uint32_t g) __attribute__((always_inline)) {
+    for (; g < NG; g += WG) {
+      const uint64_t s = S0 + (uint64_t)g * G;
+      lds[Geo::padded(g)] = m.next(load_granule<InT, VEC>(in, s, p.L), s);
+    }
+  };
+  if (p.hist != nullptr && (int64_t)S0 + p.in_off < 0) {  // uniform: the tile starts in the stream's history
+    stage_history<InT, Geo, WG>(lds, in, S0, NG, p, m);
+    return;
+  }
+  const uint32_t tid = threadIdx.x;
+  // wave-uniform: is the whole staged span readable? (not the first tile of an anchored call starting inside its
+  // cell, not the last tile)
+  const bool whole = VEC && (int64_t)S0 >= 0 && (S0 + (uint64_t)NG * G <= p.L);
+  if constexpr (SH != 0 && std::is_same<InT, float>::value) {
+    // real samples SH (1..3) floats off 16-byte alignment (4-byte aligned): aligned 16-byte loads from
+    // SH samples early; loaded quad g holds the last SH samples of granule g - 1 and the first 4 - SH of
+    // granule g, written as two partial-granule LDS stores (8-byte aligned pieces). The halo re-writes
+    // the body's last granule whole, as for complex input.
+    static_assert(!VEC && SH > 0 && SH < 4, "shifted real staging: 1..3 floats off 16-byte alignment");
+    // (a tile less than SH samples past the start of the caller's buffer would load samples before it --
+    // inside its first 16-byte block, so it cannot fault, but it is out of bounds: that tile takes the
+    // per-granule loads below instead. The buffer starts at `in - in_off` on the streaming path.)
+    if ((int64_t)S0 + p.in_off >= (int64_t)SH && S0 + (uint64_t)NG * G <= p.L) {
+      float* __restrict__ l1 = reinterpret_cast<float*>(lds);
+#pragma unroll
+      for (int b0 = 0; b0 < BPT; b0 += SB) {
+        float4 v[SB];
+        load_batch<InT, SB, WG, NT>(v, in + S0 - SH, b0 * WG + tid);  // 16-byte aligned
+#pragma unroll
+        for (int k = 0; k < SB; ++k) {
+          const uint32_t g = (b0 + k) * WG + tid;
+          float* __restrict__ lo = l1 + 4 * Geo::padded(g);  // granule g
+          if constexpr (SH == 2) {
+            if (g > 0) *reinterpret_cast<float2*>(l1 + 4 * Geo::padded(g - 1) + 2) = make_float2(v[k].x, v[k].y);
+            *reinterpret_cast<float2*>(lo) = make_float2(v[k].z, v[k].w);
+          } else if constexpr (SH == 1) {
+            if (g > 0) l1[4 * Geo::padded(g - 1) + 3] = v[k].x;
+            *reinterpret_cast<float2*>(lo) = make_float2(v[k].y, v[k].z);
+            lo[2] = v[k].w;
           } else {
-            set_zero(v[b][c]);
+            if (g > 0) {
+              float* __restrict__ pv = l1 + 4 * Geo::padded(g - 1);
+              pv[1] = v[k].x;
+              *reinterpret_cast<float2*>(pv + 2) = make_float2(v[k].y, v[k].z);
+            }
+            lo[0] = v[k].w;
           }
         }
       }
-#pragma unroll
-      for (int b = 0; b < B; ++b) {
-        const uint32_t g = g0 + (uint32_t)b * WG + tid;
-        if (g0 + (uint32_t)b * WG > 0) e = cmul(e, F);
-        if (g >= NG) break;
-        const float2 a = to_lds_sample(v[b][0]), c = to_lds_sample(v[b][1]);
-        lds[Geo::padded(g)] = rel_mix(make_float4(a.x, a.y, c.x, c.y), e, w);
-      }
+      stage_halo(BPT * WG - 1 + tid);
+      return;
     }
-    return;
-  }
-  if constexpr (SH != 0) {
-    static_assert(!VEC && SH == 1, "shifted staging is for 8-byte-aligned complex or 2-byte-aligned int8 I/Q input");
+  } else if constexpr (SH != 0) {
+    static_assert((std::is_same<InT, float2>::value || std::is_same<InT, Iq8>::value) && !VEC && SH == 1,
+                  "shifted staging is for 8-byte-aligned complex or 2-byte-aligned int8 I/Q input");
+    // (a tile starting at the caller's buffer, chunk = in - in_off, would load the sample before it)
     if ((int64_t)S0 + p.in_off >= 1 && S0 + (uint64_t)NG * G <= p.L) {
-      // loaded pair g holds samples 2g - 1 (the odd half of granule g - 1: lane l - 1's chain, or for lane 0
-      // lane WG - 1's chain one row behind) and 2g (granule g): the previous lane's chain runs beside this one
-      const uint32_t lp = (lane + WG - 1) % WG;
-      const bool lag = lane == 0 && row == 0;  // lane 0 of a cell's first row has no previous granule in the cell
-      float2 ep = nco_direct((2u * lp) * p.nco_inc);
-      for (uint32_t i = 0; i < row; ++i) {
-        const float2 t = cmul(ep, F);
-        ep = (lane == 0 && i == 0) ? ep : t;  // lane 0 follows lane WG - 1 one row behind
-      }
+      auto prev = m.begin_shifted();
       float2* __restrict__ l2 = reinterpret_cast<float2*>(lds);
 #pragma unroll
       for (int b0 = 0; b0 < BPT; b0 += SB) {
         float4 v[SB];
-        if constexpr (std::is_same<InT, Iq8>::value) {
-          const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(in + S0 - 1);  // 4-byte aligned
-          uint32_t wd[SB];
-#pragma unroll
-          for (int k = 0; k < SB; ++k) {
-            wd[k] = NT ? __builtin_nontemporal_load(src + (b0 + k) * WG + tid) : src[(b0 + k) * WG + tid];
-          }
-#pragma unroll
-          for (int k = 0; k < SB; ++k) v[k] = iq8x2_granule(wd[k]);
-        } else {
-          const float4* __restrict__ src = reinterpret_cast<const float4*>(in + S0 - 1);  // 16-byte aligned
-#pragma unroll
-          for (int k = 0; k < SB; ++k) v[k] = NT ? load16_nt(src + (b0 + k) * WG + tid) : src[(b0 + k) * WG + tid];
-        }
+        load_batch<InT, SB, WG, NT>(v, in + S0 - 1, b0 * WG + tid);  // complex: 16-byte aligned, int8 I/Q: 4-byte
 #pragma unroll
         for (int k = 0; k < SB; ++k) {
-          const int row = b0 + k;
-          const uint32_t g = (uint32_t)row * WG + tid;
-          if (row > 0) {
-            e = cmul(e, F);
-            const float2 t = cmul(ep, F);
-            ep = (row == 1 && lag) ? ep : t;
-          }
-          const float2 a = cmul(make_float2(v[k].x, v[k].y), cmul(ep, w));  // sample 2g - 1
-          const float2 b = cmul(make_float2(v[k].z, v[k].w), e);            // sample 2g
-          if (g > 0) l2[2 * Geo::padded(g - 1) + 1] = a;
-          l2[2 * Geo::padded(g)] = b;
+          const uint32_t g = (b0 + k) * WG + tid;
+          const float4 w = m.shifted_row(v[k], b0 + k, prev);
+          if (g > 0) l2[2 * Geo::padded(g - 1) + 1] = make_float2(w.x, w.y);
+          l2[2 * Geo::padded(g)] = make_float2(w.z, w.w);
         }
       }
-      // the halo (its first granule rewrites the body's last slot whole): granule g of this loop is lane l - 1's
-      // (lane 0: lane WG - 1's, one row back), i.e. the previous-lane chain's
-      for (uint32_t g = BPT * WG - 1 + tid; g < NG; g += WG) {
-        ep = cmul(ep, F);
-        lds[Geo::padded(g)] = rel_mix(load_granule<InT, false>(in, S0 + (uint64_t)g * G, p.L), ep, w);
-      }
+      m.shifted_halo(prev);
+      stage_halo(BPT * WG - 1 + tid);  // (its first granule rewrites the body's last slot whole)
       return;
     }
   }
-  // wave-uniform: is the whole staged span readable? (not the first tile of a call starting inside its cell, not
-  // the last)
-  const bool whole = VEC && (int64_t)S0 >= 0 && (S0 + (uint64_t)NG * G <= p.L);
+  if constexpr (DMA) {
+    if (whole && stage_body_dma<InT, Geo, WG, MIXED, NT>(lds, in, S0)) {
+      stage_halo(BPT * WG + tid);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      return;
+    }
+  }
+  HaloPre<InT, VEC> halo(S0, BPT * WG + tid, NG, p.L);
   const uint32_t pbase = Geo::padded(tid);
-  HaloPre<InT, VEC> halo(S0, BPT * WG + tid, NG, p.L);  // (HaloPre)
+  m.per_parity([&](auto odd) {
 #pragma unroll
-  for (int b0 = 0; b0 < BPT; b0 += SB) {
-    float4 v[SB];
-    if (whole) {
-      if constexpr (std::is_same<InT, Iq8>::value) {
-        const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(in + S0);
-        uint32_t wd[SB];
+    for (int b0 = 0; b0 < BPT; b0 += SB) {
+      float4 v[SB];
+      if (whole) {
+        load_batch<InT, SB, WG, NT>(v, in + S0, b0 * WG + tid);
+      } else {
 #pragma unroll
         for (int k = 0; k < SB; ++k) {
-          wd[k] = NT ? __builtin_nontemporal_load(src + (b0 + k) * WG + tid) : src[(b0 + k) * WG + tid];
+          v[k] = load_granule<InT, VEC>(in, S0 + (uint64_t)((b0 + k) * WG + tid) * G, p.L);
         }
-#pragma unroll
-        for (int k = 0; k < SB; ++k) v[k] = iq8x2_granule(wd[k]);
-      } else {
-        const float4* __restrict__ src = reinterpret_cast<const float4*>(in + S0);
-#pragma unroll
-        for (int k = 0; k < SB; ++k) v[k] = NT ? load16_nt(src + (b0 + k) * WG + tid) : src[(b0 + k) * WG + tid];
       }
-    } else {
+      if (b0 == 0) halo.issue(in);
 #pragma unroll
       for (int k = 0; k < SB; ++k) {
-        v[k] = load_granule<InT, VEC>(in, S0 + (uint64_t)((b0 + k) * WG + tid) * G, p.L);
+        const uint32_t g = (b0 + k) * WG + tid;
+        // padded(k * WG + tid) = padded(tid) + k * padded(WG) when whole segments fit a workgroup's row of
+        // granules: a per-thread base plus an immediate offset per granule
+        const uint32_t slot = (WG % Geo::SG == 0) ? pbase + (uint32_t)(b0 + k) * Geo::padded(WG) : Geo::padded(g);
+        lds[slot] = m.row(v[k], b0 + k, odd);
       }
     }
-    if (b0 == 0) halo.issue(in);
-#pragma unroll
-    for (int k = 0; k < SB; ++k) {
-      if (b0 + k > 0) e = cmul(e, F);
-      const uint32_t g = (b0 + k) * WG + tid;
-      const uint32_t slot = (WG % Geo::SG == 0) ? pbase + (uint32_t)(b0 + k) * Geo::padded(WG) : Geo::padded(g);
-      lds[slot] = rel_mix(v[k], e, w);
-    }
-  }
-  if (halo.g < NG) {
-    e = cmul(e, F);
-    lds[Geo::padded(halo.g)] = rel_mix(halo.get(in, p.L), e, w);
-  }
-  for (uint32_t g = halo.g + WG; g < NG; g += WG) {
-    e = cmul(e, F);
-    lds[Geo::padded(g)] = rel_mix(load_granule<InT, VEC>(in, S0 + (uint64_t)g * G, p.L), e, w);
-  }
+  });
+  if (halo.g < NG) lds[Geo::padded(halo.g)] = m.next(halo.get(in, p.L), halo.s);
+  stage_halo(halo.g + WG);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1312,8 +1239,7 @@ __device__ __forceinline__ bool all_finite(const float (&acc)[R]) {
 // Kernel 1: polyphase-granule kernel, one tile per workgroup (D a multiple of the granule width G).
 // ABL (ablation, tuning probes only): low bits 0 = full kernel, 1 = staging only, 2 = compute only;
 // chain-mode flags 8 = staging without the NCO mix, 16 = plain float store instead of the FM
-// discriminator, 32 = NCO mix without the per-granule transcendental pair, 128 = tile-relative phasors
-// by recurrence; 64 = register window from the thread's own R rows only (wrong results: LDS-read probe).
+// discriminator, 64 = register window from the thread's own R rows only (wrong results: LDS-read probe).
 // NT: non-temporal (streaming) HBM loads for the staged input.
 // ------------------------------------------------------------------------------------------------
 // Tile of workgroup b. XCD-aware (XM): workgroups are dispatched round-robin over the 8 XCDs, so
@@ -1332,7 +1258,7 @@ __device__ __forceinline__ uint32_t tile_of_block() {
 }
 
 // One tile of the polyphase kernel (the body of k_fir_poly and of k_fir_poly_grouped). FM / AM tiles are
-// anchored (stage_tile_rel): tile t covers outputs [t S - tile_shift, t S - tile_shift + KT) with S = tile_stride
+// anchored (MixAnchored): tile t covers outputs [t S - tile_shift, t S - tile_shift + KT) with S = tile_stride
 // (KT for AM; KT - R for FM, whose last thread's outputs only serve as the discriminator partners of the one before,
 // so every discriminator pairs two outputs of one tile in one NCO frame) and is sub-tile (cell_sub0 + t) mod SUBS of
 // its NCO cell of SUBS tiles.
@@ -1355,15 +1281,15 @@ __device__ __forceinline__ void fir_poly_tile(const FirParams& p, uint32_t tile)
   const uint32_t span = p.nch * JC * D;
   const uint32_t NG = ((Geo::KT - 1) * D + span + G - 1) / G;
   // LDS: [tile granules | FM exchange (WG float2)]
-  constexpr int SMODE = (ABL & 8) ? (int)kModeFir : MODE;
   if constexpr ((ABL & 7) != 2) {
-    if constexpr (ANCH && SMODE != kModeFir) {
+    if constexpr (ANCH && (ABL & 8) == 0) {
       // the tile is sub-tile `sub` of its NCO cell: it starts sub (KT - R) outputs (FM) or sub KT outputs (AM) into
-      // the cell, i.e. sub BPT granule rows in, less sub SG granules for FM (stage_tile_rel)
+      // the cell, i.e. sub BPT granule rows in, less sub SG granules for FM (MixAnchored)
       const uint32_t sub = (p.cell_sub0 + tile) % SUBS;
-      stage_tile_rel<InT, Geo, WG, VEC, NT, SH>(lds, in, S0, NG, p, sub * BPT, MODE == kModeFm ? sub * Geo::SG : 0u);
+      stage_tile<InT, Geo, WG, VEC, NT, DMA, SH>(
+          lds, in, S0, NG, p, MixAnchored<WG>(p.nco_inc, sub * BPT, MODE == kModeFm ? sub * Geo::SG : 0u));
     } else {
-      stage_tile<InT, Geo, WG, VEC, SMODE, NT, DMA, SH>(lds, in, S0, NG, p);
+      stage_tile<InT, Geo, WG, VEC, NT, DMA, SH>(lds, in, S0, NG, p, MixNone{});
     }
   }
   __syncthreads();
@@ -1462,7 +1388,11 @@ __global__ __launch_bounds__(WG) void k_fir_contig(FirParams p) {
   const uint32_t span = p.nch * IC;
   const uint32_t NG = ((Geo::KT - 1) * D + span + G - 1) / G;
 
-  stage_tile<InT, Geo, WG, VEC, MODE, false, false, SH>(lds, in, S0, NG, p);
+  if constexpr (MODE == kModeFir) {
+    stage_tile<InT, Geo, WG, VEC, false, false, SH>(lds, in, S0, NG, p, MixNone{});
+  } else {
+    stage_tile<InT, Geo, WG, VEC, false, false, SH>(lds, in, S0, NG, p, MixAbsolute<InT, MODE, WG>(p, S0));
+  }
   __syncthreads();
   stream_history_store<InT>(p, hist);
 
@@ -1742,7 +1672,7 @@ __global__ __launch_bounds__(WG) void k_fir_mfma_bc(FirParams p) {
     const uint32_t i = 16u * c + (lane >> 2) - D * (lane & 3u);  // wraps (>= T) below zero
     tv[c] = i < p.T ? taps[i] : 0.0f;
   }
-  if constexpr (ABL != 2) stage_tile<float2, Geo, WG, VEC, kModeFir, NT>(lds, in, S0, NG, p);
+  if constexpr (ABL != 2) stage_tile<float2, Geo, WG, VEC, NT>(lds, in, S0, NG, p, MixNone{});
   __syncthreads();
 
   const float4* __restrict__ seg = lds + tid * Geo::SGP;

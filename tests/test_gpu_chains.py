@@ -132,6 +132,79 @@ def test_chain_split_straddles_2_pow_32_outputs(cuda, kind, D):
     assert torch.equal(chunked(n0, (1500, N - 1500)), above)
 
 
+def misaligned(x):
+    """The same samples one sample (8 bytes) off 16-byte alignment (run_fir's construction, test_gpu_fir.py)."""
+    y = torch.cat([torch.zeros(1, dtype=x.dtype, device=x.device), x])[1:]
+    assert x.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 8
+    return y
+
+
+def d4_outputs(cuda, tiles):
+    """An output count that reaches launch_poly_d4's tile shape `tiles` on this device: "tiles256" (256-output
+    tiles, three NCO cells), "tiles512" (140,001 outputs, or more on a device with more CUs), "tiles1024" (just
+    inside the 1,024-output tiles)."""
+    slots = 4 * torch.cuda.get_device_properties(cuda).multi_processor_count
+    n256, n512, n1024 = 3 * 1020 + 7, max(140_001, 256 * (slots // 2) + 1), 3 * slots * 1024 + 1
+    assert 2 * -(-n256 // 256) <= slots < 2 * -(-n512 // 256), (n256, n512, slots)
+    assert -(-n512 // 1024) < 3 * slots <= -(-n1024 // 1024), (n512, n1024, slots)
+    return {"tiles256": n256, "tiles512": n512, "tiles1024": n1024}[tiles]
+
+
+@pytest.mark.parametrize("D,N", [(1, 2 * 4096 + 11), (3, 2 * 4096 + 11), (2, 2 * 4096 + 11), (4, "tiles256"),
+                                 (4, "tiles512"), (6, 2 * 4096 + 11), (8, 2 * 4096 + 11), (20, 2 * 4096 + 11)])
+@pytest.mark.parametrize("kind", ["fm", "am"])
+def test_chain_float_misaligned_bit_identical(cuda, kind, D, N):
+    """Float FM / AM with the input 8 bytes off 16-byte alignment (the shifted staging of complex samples: for the
+    anchored polyphase tiles the previous lane's phasor chain beside the thread's own; for the absolute mixer of
+    D = 1, 3 the odd-start pairs) equals the aligned call bit for bit, and the aligned call meets the oracle.
+    n0 = 1333 D + 1 puts output 0 inside its tile (at D = 4: tile shift 58 (FM) / 53 (AM) in sub-tile 1 of its NCO
+    cell), so the first tile starts before the buffer and drops off the shifted path, and the odd n0 starts the
+    absolute mixer on the odd parity. D = 4 runs its 256-output (SUBS = 4, three cells) and 512-output (SUBS = 2)
+    tile shapes."""
+    from gsdr_amd import ops
+    from gsdr_amd.signals import fm_test_signal, lowpass_taps, uniform_iq
+
+    T, n0, fm = 31, D * 1333 + 1, kind == "fm"
+    if isinstance(N, str):
+        N = d4_outputs(cuda, N)
+    L = (N if fm else N - 1) * D + T
+    x_np = fm_test_signal(L, fs=FS, noise=0.05, seed=D) if fm else (0.7 * uniform_iq(L, seed=D)).astype(np.complex64)
+    taps_np = lowpass_taps(T, 0.1)
+    x, taps = dev(x_np, cuda), dev(taps_np, cuda)
+
+    def call(xs):
+        if fm:
+            return ops.fm_demod(xs, taps, FS, TUNE, CHAN, DEV, D, n0, N)
+        return ops.am_demod(xs, taps, FS, TUNE, CHAN, D, n0, N)
+
+    aligned, shifted = call(x), call(misaligned(x))
+    torch.cuda.synchronize()
+    got = aligned.cpu().numpy()
+    assert shifted.cpu().numpy().tobytes() == got.tobytes()
+    if fm:
+        err = wrapped_angle_err(got, o.fm_demod(x_np, taps_np, FS, TUNE, CHAN, DEV, D, n0, N), fm_gain())
+    else:
+        err = float(np.max(np.abs(got - o.am_demod(x_np, taps_np, FS, TUNE, CHAN, D, n0, N))))
+    print(f"{kind} D={D} N={N}: error {err:.3e} (bar {FLOAT_TOL:.1e})")
+    assert err <= FLOAT_TOL
+
+
+def test_chain_float_misaligned_bit_identical_1024_tiles(cuda):
+    """The same at D = 4, FM, on the 1,024-output tiles (a call just past launch_poly_d4's threshold): misaligned
+    against aligned bytes only."""
+    from gsdr_amd import ops
+    from gsdr_amd.signals import lowpass_taps
+
+    D, T, n0 = 4, 31, 4 * 1333 + 1
+    N = d4_outputs(cuda, "tiles1024")
+    gen = torch.Generator(device=cuda).manual_seed(4)
+    x = torch.view_as_complex(torch.rand(N * D + T, 2, device=cuda, generator=gen) - 0.5)
+    taps = dev(lowpass_taps(T, 0.1), cuda)
+    aligned = ops.fm_demod(x, taps, FS, TUNE, CHAN, DEV, D, n0, N)
+    shifted = ops.fm_demod(misaligned(x), taps, FS, TUNE, CHAN, DEV, D, n0, N)
+    assert torch.equal(aligned.view(torch.int32), shifted.view(torch.int32))
+
+
 def test_fm_pure_tone_known_answer(cuda):
     """A noiseless FM carrier at a constant offset f from the channel discriminates to the constant
     g * 2 pi f D'/fs where the discriminator sees decimated samples: arg step = 2 pi f D / fs."""
