@@ -24,7 +24,7 @@ gsdr_amd/libgsdr.so: $(OBJS)
 
 # Tuning-probe build: the product objects with fir.hip (ablation variants >= 100 of gsdrxFirFCVariant) and iir.hip
 # (the single-pass IIR, gsdrxIirFFSinglePass / CC) recompiled under GSDR_TUNING_PROBES. Loaded by tools/, by
-# bench.py's staging-ceiling leg and by tests/test_gpu_iir_single_pass.py; never by the product path.
+# bench.py's staging-ceiling leg and by tests/test_gpu_iir.py; never by the product path.
 probes: $(BUILD)/probes/libgsdr_probes.so
 
 PROBE_SRCS := fir iir

@@ -169,8 +169,8 @@ hipError_t launch_generic(const FirJob& j, hipStream_t s) {
   return launch_status();
 }
 
-// Tile grid of the polyphase kernels. FIR: tile t = outputs [t KT, (t + 1) KT). FM / AM chains (anchored NCO,
-// fir_engine.hpp MixAnchored): tiles on an absolute output grid of stride S -- KT for AM; KT - R for FM, whose
+// Tile grid of the polyphase kernels. FIR: tile t = outputs [t KT, (t + 1) KT). FM / AM / IQ chains (anchored NCO,
+// fir_engine.hpp MixAnchored): tiles on an absolute output grid of stride S -- KT for AM and IQ; KT - R for FM, whose
 // tiles overlap by one thread's outputs so that every discriminator pairs two outputs of one tile -- output 0
 // (absolute index q0) sits at tile_shift = q0 mod S in tile 0, which is sub-tile cell_sub0 of its NCO cell of
 // SUBS tiles (CELL = SUBS S outputs; the short-call shapes of a decimation are sub-tiles of its largest tile, whose
@@ -666,8 +666,10 @@ hipError_t launch_fir(const FirJob& j, hipStream_t s) {
       if (j.D == 4 && j.variant >= 0) return launch_d4_int8(j, s);
     }
     // D = 4 FM / AM chains: the matrix-core kernel with the NCO folded into complex taps (normwise
-    // parity with the float chains: DESIGN.md section 3.3); variant 0 keeps the exact path (streams)
-    if constexpr (MODE != kModeFir && std::is_same<TapT, float>::value) {
+    // parity with the float chains: DESIGN.md section 3.3); variant 0 keeps the exact path (streams). The
+    // frequency-translating FIR (kModeIq) has no matrix-core form: at every decimation it takes the float-input
+    // shapes below, so its int8 outputs are those of the converted float input bit for bit.
+    if constexpr ((MODE == kModeFm || MODE == kModeAm) && std::is_same<TapT, float>::value) {
       if (j.D == 4 && j.variant < 0 && !j.stream_tiled && j.T <= (size_t)I8ChainMfma<MODE>::MAXT) {
         return launch_chain_i8_mfma<MODE>(j, s);
       }

@@ -181,7 +181,7 @@ __device__ __forceinline__ float2 tap_at<float2>(const TapBuf& tb, int i) {
 // ------------------------------------------------------------------------------------------------
 // Launch parameters (one struct for every mode; passed by value)
 // ------------------------------------------------------------------------------------------------
-// (enum Mode { kModeFir, kModeFm, kModeAm }: stream_step.hpp)
+// (enum Mode { kModeFir, kModeFm, kModeAm, kModeIq }: stream_step.hpp)
 struct FirParams {
   const void* in;
   const void* taps;
@@ -196,7 +196,7 @@ struct FirParams {
   uint32_t nco_n0;       // low 32 bits of firstSampleIndex
   float fm_gain;         // FM discriminator gain
   uint32_t out_phase;    // absolute index of output 0 mod 16 (the int8 matrix-core kernels' block grid)
-  // Anchored chains (the polyphase kernels in FM / AM mode, anchored_nco below): tile t covers outputs
+  // Anchored chains (the polyphase kernels in FM / AM / IQ mode, MixAnchored below): tile t covers outputs
   // [t KT - tile_shift, (t + 1) KT - tile_shift) of the call, and tile 0 is sub-tile cell_sub0 of its NCO cell.
   uint32_t tile_shift;
   uint32_t cell_sub0;
@@ -587,7 +587,8 @@ struct MixAbsolute {
 // scheme's transcendental pair, and every phasor a fixed sequence of operations on (l, k) alone. The
 // short-call tiles are sub-tiles of a cell that start their chains at row r0 by r0 multiplies, and every
 // staging path (aligned, shifted, streaming) forms the same values, so every tile shape and any split of a
-// stream into calls give bit-identical outputs.
+// stream into calls give bit-identical outputs. (IQ mode, whose complex output does see the
+// rotation, undoes it per cell in the epilogue: anchor_rotate below.)
 // ------------------------------------------------------------------------------------------------
 template <int WG>
 __device__ __forceinline__ float2 rel_chain_start(uint32_t lane, uint32_t rows, uint32_t inc) {
@@ -660,6 +661,21 @@ struct MixAnchored {
   // chain's
   __device__ __forceinline__ void shifted_halo(const Prev& q) { e = q.ep; }
 };
+
+// A complex output (kModeIq) is not invariant to the anchor: a cell's FIR outputs, accumulated from samples mixed
+// relative to the cell's first sample, are the absolute-phase outputs times conj(A), A = the absolute phasor of that
+// sample, so the epilogue multiplies each by A. cell_out0 = the call-local index of the cell's first output (low 32
+// bits; below zero, wrapped, for a call that starts inside a cell): its first sample is absolute sample
+// n_anchor = nco_n0 + cell_out0 D mod 2^32 -- the same integer from whichever call, tile shape or sub-tile reaches
+// the cell -- and A = nco_direct(n_anchor inc) a function of it alone, applied by one cmul(acc, A) per output. The
+// rotated outputs therefore keep the anchored accumulators' property: the same bits for the same absolute output.
+template <int R>
+__device__ __forceinline__ void anchor_rotate(const FirParams& p, uint32_t cell_out0, uint32_t D, float2 (&acc)[R]) {
+  const uint32_t n_anchor = p.nco_n0 + cell_out0 * D;
+  const float2 A = nco_direct(n_anchor * p.nco_inc);
+#pragma unroll
+  for (int r = 0; r < R; ++r) acc[r] = cmul(acc[r], A);
+}
 
 // A streaming call's first tile, which reaches into the stream's history (only that tile: the history is shorter
 // than one window). Local sample s (counted from output 0's window start, `in` = chunk + in_off) is chunk sample
@@ -848,9 +864,11 @@ __device__ __forceinline__ void store16_nt(float4* p, float4 v) {
 template <class OutT, int R, bool NTS = false>
 __device__ __forceinline__ void store_fir(OutT* __restrict__ out, uint64_t k0, uint64_t N, const OutT (&acc)[R]) {
   constexpr int PER16 = 16 / sizeof(OutT);
-  // 16-byte stores when R fills them (a thread's outputs are contiguous), else one output at a time
+  // 16-byte stores when R fills them (a thread's outputs are contiguous), else one output at a time.
+  // (k0 < N first: an anchored tile's leading outputs (kModeIq) have k0 wrapped below zero, and k0 + R would wrap
+  // back into range; the anchored grid's tile_shift may also leave the address 8 bytes off, then the scalar stores)
   if constexpr (R % PER16 == 0) {
-    if (k0 + R <= N && (reinterpret_cast<uintptr_t>(out + k0) & 15u) == 0) {
+    if (k0 < N && N - k0 >= (uint64_t)R && (reinterpret_cast<uintptr_t>(out + k0) & 15u) == 0) {
       float4* o = reinterpret_cast<float4*>(out + k0);
 #pragma unroll
       for (int q = 0; q < R / PER16; ++q) {
@@ -1031,7 +1049,9 @@ __device__ __forceinline__ void tile_epilogue(const FirParams& p, uint64_t out0,
                                               float4* tile = nullptr) {
   const uint32_t t = threadIdx.x;
   const uint32_t local0 = t * R;
-  if constexpr (MODE == kModeFir) {
+  if constexpr (MODE == kModeFir || MODE == kModeIq) {
+    // (kModeIq: the FIR store behind the NCO staging; the anchored tiles have rotated acc to the absolute phase,
+    // anchor_rotate)
     store_fir<OutT, R, NTS>(reinterpret_cast<OutT*>(p.out), out0 + local0, p.N, acc);
   } else if constexpr (MODE == kModeAm) {
     float o[R];
@@ -1281,11 +1301,11 @@ __device__ __forceinline__ void fir_poly_tile(const FirParams& p, uint32_t tile)
   const uint32_t span = p.nch * JC * D;
   const uint32_t NG = ((Geo::KT - 1) * D + span + G - 1) / G;
   // LDS: [tile granules | FM exchange (WG float2)]
+  // the tile is sub-tile `sub` of its NCO cell: it starts sub (KT - R) outputs (FM) or sub KT outputs (AM, IQ) into
+  // the cell, i.e. sub BPT granule rows in, less sub SG granules for FM (MixAnchored)
+  const uint32_t sub = ANCH ? (p.cell_sub0 + tile) % SUBS : 0u;
   if constexpr ((ABL & 7) != 2) {
     if constexpr (ANCH && (ABL & 8) == 0) {
-      // the tile is sub-tile `sub` of its NCO cell: it starts sub (KT - R) outputs (FM) or sub KT outputs (AM) into
-      // the cell, i.e. sub BPT granule rows in, less sub SG granules for FM (MixAnchored)
-      const uint32_t sub = (p.cell_sub0 + tile) % SUBS;
       stage_tile<InT, Geo, WG, VEC, NT, DMA, SH>(
           lds, in, S0, NG, p, MixAnchored<WG>(p.nco_inc, sub * BPT, MODE == kModeFm ? sub * Geo::SG : 0u));
     } else {
@@ -1308,6 +1328,10 @@ __device__ __forceinline__ void fir_poly_tile(const FirParams& p, uint32_t tile)
     if constexpr (ABL == 0) {
       if (!all_finite(acc)) poly_fixup<TapT, InT, D, R, JC, WG>(lds, p, acc);
     }
+  }
+  if constexpr (MODE == kModeIq && (ABL & 8) == 0) {
+    // back to the absolute phase: the cell's first output is sub * tile_stride outputs before the tile's
+    anchor_rotate(p, (uint32_t)out0 - sub * p.tile_stride, D, acc);
   }
 
   if constexpr (CST != 0 && MODE == kModeFir) {
@@ -1361,7 +1385,9 @@ __global__ __launch_bounds__(WG) void k_fir_poly_grouped(FirParams p, MultiParam
   FirParams pc = p;
   pc.nco_inc = mp.inc[c];
   pc.fm_gain = mp.gain[c];
-  pc.out = reinterpret_cast<float*>(p.out) + (uint64_t)c * mp.out_stride;
+  // (out_stride counts outputs: floats for FM / AM, complex elements for the frequency-translating FIR)
+  using ChanOutT = std::conditional_t<MODE == kModeIq, float2, float>;
+  pc.out = reinterpret_cast<ChanOutT*>(p.out) + (uint64_t)c * mp.out_stride;
   if (c != 0) pc.hist_out = nullptr;  // a multi-channel stream step: channel 0's workgroup 0 copies the history
   fir_poly_tile<TapT, InT, D, R, JC, WG, VEC, MODE, 0, true, 0, false, SH, 1>(pc, tile);
 }
@@ -1606,7 +1632,7 @@ __global__ __launch_bounds__(256) void k_fir_generic(FirParams p) {
   using OutT = typename Product<TapT, InT>::type;
   const uint64_t k = (uint64_t)blockIdx.x * 256u + threadIdx.x;
   if (k >= p.N) return;
-  if constexpr (MODE == kModeFir) {
+  if constexpr (MODE == kModeFir || MODE == kModeIq) {
     reinterpret_cast<OutT*>(p.out)[k] = fir_point<TapT, InT, MODE>(p, k);
   } else if constexpr (MODE == kModeAm) {
     reinterpret_cast<float*>(p.out)[k] = am_env(fir_point<TapT, InT, MODE>(p, k));

@@ -89,6 +89,12 @@ hipError_t filter(const gsdrxStream_t& s, size_t c, const void* in, uint64_t fir
                                    static_cast<const int8_t*>(in), static_cast<float*>(out), n, s.device, st)
                 : gsdrFmDemod(s.fs, s.tune, chan, dev, s.D, first, s.taps, s.T,
                               static_cast<const hipFloatComplex*>(in), static_cast<float*>(out), n, s.device, st);
+    case GSDRX_STREAM_XLATE:
+      return i8 ? gsdrxXlatingFirInt8(s.fs, s.tune, chan, s.D, first, s.taps, s.T, static_cast<const int8_t*>(in),
+                                      static_cast<hipFloatComplex*>(out), n, s.device, st)
+                : gsdrxXlatingFir(s.fs, s.tune, chan, s.D, first, s.taps, s.T,
+                                  static_cast<const hipFloatComplex*>(in), static_cast<hipFloatComplex*>(out), n,
+                                  s.device, st);
     default:
       return i8 ? gsdrxAmDemodInt8(s.fs, s.tune, chan, s.D, first, s.taps, s.T,
                                    static_cast<const int8_t*>(in), static_cast<float*>(out), n, s.device, st)
@@ -153,6 +159,9 @@ hipError_t channel_step(const gsdrxStream_t& s, const ChainSpec& cs, size_t c, c
     return i8 ? fir_int8_stream_step_tiled(s.D, s.taps, s.T, so, o, n, s.device, st)
               : fir_fc_stream_step(s.D, s.taps, s.T, so, o, n, s.device, st);
   }
+  if (s.kind == GSDRX_STREAM_XLATE) {  // (no matrix-core form: int8 I/Q takes the tiled kernels at every decimation)
+    return xlate_stream_step_tiled(cs, i8, s.chans[c], so, static_cast<hipFloatComplex*>(out), n, s.device, st);
+  }
   float* o = static_cast<float*>(out);
   if (i8) e = chain_int8_stream_step(cs, s.chans[c], s.devs[c], so, o, n, s.device, st);
   if (e != hipErrorNotSupported) return e;
@@ -187,7 +196,9 @@ hipError_t create_stream(gsdrxStream* stream, int kind, int sampleFormat, uint32
   if (stream == nullptr) return hipErrorInvalidValue;
   *stream = nullptr;
   if (decimation == 0 || tapCount == 0 || taps == nullptr || count == 0) return hipErrorInvalidValue;
-  if (kind != GSDRX_STREAM_FIR && kind != GSDRX_STREAM_FM && kind != GSDRX_STREAM_AM) return hipErrorInvalidValue;
+  if (kind != GSDRX_STREAM_FIR && kind != GSDRX_STREAM_FM && kind != GSDRX_STREAM_AM && kind != GSDRX_STREAM_XLATE) {
+    return hipErrorInvalidValue;
+  }
   if (sampleFormat != GSDRX_SAMPLES_CF32 && sampleFormat != GSDRX_SAMPLES_CS8) return hipErrorInvalidValue;
   gsdrxStream s = new (std::nothrow) gsdrxStream_t;
   if (s == nullptr) return hipErrorOutOfMemory;
@@ -209,7 +220,7 @@ hipError_t create_stream(gsdrxStream* stream, int kind, int sampleFormat, uint32
   s->n0 = firstSampleIndex;
   s->device = cudaDevice;
   s->sb = sampleFormat == GSDRX_SAMPLES_CS8 ? 2 : 8;
-  s->ob = kind == GSDRX_STREAM_FIR ? 8 : 4;
+  s->ob = (kind == GSDRX_STREAM_FIR || kind == GSDRX_STREAM_XLATE) ? 8 : 4;
   DeviceScope scope(cudaDevice);
   hipError_t e = scope.status();
   const size_t hist_bytes = s->W * s->sb;  // history < W samples
@@ -241,11 +252,11 @@ GSDR_C_LINKAGE hipError_t gsdrxStreamCreateMulti(gsdrxStream* stream, int kind, 
                                                  const float* frequencyDeviations, uint32_t numChannels,
                                                  size_t firstSampleIndex, int32_t cudaDevice) GSDR_NO_EXCEPT {
   if (stream != nullptr) *stream = nullptr;
-  if (kind != GSDRX_STREAM_FM && kind != GSDRX_STREAM_AM) return hipErrorInvalidValue;
+  if (kind != GSDRX_STREAM_FM && kind != GSDRX_STREAM_AM && kind != GSDRX_STREAM_XLATE) return hipErrorInvalidValue;
   if (numChannels == 0 || channelFrequencies == nullptr) return hipErrorInvalidValue;
   if (kind == GSDRX_STREAM_FM && frequencyDeviations == nullptr) return hipErrorInvalidValue;
   std::vector<float> ones;
-  if (frequencyDeviations == nullptr) {  // AM: deviations unused
+  if (frequencyDeviations == nullptr) {  // AM, XLATE: deviations unused
     try {
       ones.assign(numChannels, 1.0f);
     } catch (...) {
@@ -297,12 +308,19 @@ GSDR_C_LINKAGE hipError_t gsdrxStreamProcess(gsdrxStream s, const void* input, s
     so.hist_from = (int64_t)(p.m_end * s->D) - (int64_t)S;
     so.hist_n = p.hist_after;
     // (the chain part is unused by a FIR stream)
-    const gsdr::ChainSpec cs{s->kind == GSDRX_STREAM_FM ? gsdr::kModeFm : gsdr::kModeAm, s->fs, s->tune, s->D,
-                             s->n0 + h0, s->taps, s->T};
+    const int mode = s->kind == GSDRX_STREAM_FM      ? gsdr::kModeFm
+                     : s->kind == GSDRX_STREAM_XLATE ? gsdr::kModeIq
+                                                     : gsdr::kModeAm;
+    const gsdr::ChainSpec cs{mode, s->fs, s->tune, s->D, s->n0 + h0, s->taps, s->T};
     e = hipErrorNotSupported;
     if (C > 1 && s->format != GSDRX_SAMPLES_CS8) {
-      e = gsdr::chain_multi_stream_step(cs, s->chans.data(), s->devs.data(), (uint32_t)C, so,
-                                        reinterpret_cast<float*>(out), outputCapacity, n_out, s->device, cudaStream);
+      e = s->kind == GSDRX_STREAM_XLATE
+              ? gsdr::xlate_multi_stream_step(cs, s->chans.data(), (uint32_t)C, so,
+                                              reinterpret_cast<hipFloatComplex*>(out), outputCapacity, n_out,
+                                              s->device, cudaStream)
+              : gsdr::chain_multi_stream_step(cs, s->chans.data(), s->devs.data(), (uint32_t)C, so,
+                                              reinterpret_cast<float*>(out), outputCapacity, n_out, s->device,
+                                              cudaStream);
     }
     // otherwise one launch per channel; a shape without a one-launch step returns hipErrorNotSupported from
     // channel 0, before anything was launched, and the call takes the seam path below

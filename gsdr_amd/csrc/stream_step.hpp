@@ -1,6 +1,6 @@
 // gsdr-mi355x: what crosses translation units between the streaming object (stream.hip) and the files that
-// launch the filter kernels (fir.hip, fir_int8.hip, fm_am.hip). Kept free of the kernel headers, so stream.hip
-// stays cheap to compile; the defining files include it too, so a signature that drifts does not compile.
+// launch the filter kernels (fir.hip, fir_int8.hip, fm_am.hip, xlate.hip). Kept free of the kernel headers, so
+// stream.hip stays cheap to compile; the defining files include it too, so a signature that drifts does not compile.
 #pragma once
 
 #include <hip/hip_complex.h>
@@ -10,7 +10,8 @@
 
 namespace gsdr {
 
-enum Mode : int { kModeFir = 0, kModeFm = 1, kModeAm = 2 };
+// kModeIq: the chains' NCO + FIR stage with the complex output stored (gsdrxXlatingFir, xlate.hip)
+enum Mode : int { kModeFir = 0, kModeFm = 1, kModeAm = 2, kModeIq = 3 };
 
 // One streaming step's input (FirParams, fir_engine.hpp): output 0's window starts at sample in_off of the
 // chunk (negative: in the history `hist` of hist_len samples, chunk offset i < 0 being hist[hist_len + i]);
@@ -27,9 +28,10 @@ struct StreamOperands {
   uint64_t hist_n;
 };
 
-// An FM / AM chain without its channel: firstSampleIndex is the absolute index of output 0's first sample.
+// A chain (FM, AM or the frequency-translating FIR) without its channel: firstSampleIndex is the absolute index of
+// output 0's first sample.
 struct ChainSpec {
-  int mode;  // kModeFm or kModeAm
+  int mode;  // kModeFm, kModeAm or kModeIq
   float fs, tune;
   uint32_t decimation;
   uint64_t firstSampleIndex;
@@ -63,5 +65,11 @@ hipError_t chain_stream_step_tiled(const ChainSpec& cs, bool int8, float chan, f
 hipError_t chain_multi_stream_step(const ChainSpec& cs, const float* chans, const float* devs, uint32_t count,
                                    const StreamOperands& so, float* output, size_t outStride, size_t numOutputs,
                                    int32_t device, hipStream_t stream);
+// the frequency-translating FIR (kModeIq) on the tiled kernels, single channel and grouped: xlate.hip
+hipError_t xlate_stream_step_tiled(const ChainSpec& cs, bool int8, float chan, const StreamOperands& so,
+                                   hipFloatComplex* output, size_t numOutputs, int32_t device, hipStream_t stream);
+hipError_t xlate_multi_stream_step(const ChainSpec& cs, const float* chans, uint32_t count, const StreamOperands& so,
+                                   hipFloatComplex* output, size_t outStride, size_t numOutputs, int32_t device,
+                                   hipStream_t stream);
 
 }  // namespace gsdr

@@ -17,7 +17,7 @@ __all__ = [
     "qpsk_modulate_templated", "qpsk_demodulate_templated",
     "qpsk256_init", "qpsk256_modulate", "qpsk256_modulate_awgn", "qpsk256_demodulate", "qpsk256_modulate_4x", "qpsk256_demodulate_4x",
     "nco_phase_increment", "stream_of",
-    "fm_demod_multi", "am_demod_multi", "iir", "add_const", "multiply", "add_to_magnitude", "abs_", "cosine", "int8_to_norm_float",
+    "fm_demod_multi", "am_demod_multi", "xlating_fir", "xlating_fir_multi", "iir", "add_const", "multiply", "add_to_magnitude", "abs_", "cosine", "int8_to_norm_float",
 ]
 
 
@@ -152,7 +152,32 @@ def am_demod(x, taps, rf_sample_rate, tuning_frequency, channel_frequency, decim
     return out
 
 
-def _multi(name, x, taps, fs, tune, chans, devs, decimation, first_sample_index, num_outputs, fm):
+def xlating_fir(x, taps, rf_sample_rate, tuning_frequency, channel_frequency, decimation, first_sample_index=0,
+                num_outputs=None, out=None):
+    """gsdrxXlatingFir: NCO shift + low-pass FIR + decimation, the complex baseband output (gsdr_ext.h); int8 I/Q
+    input selects gsdrxXlatingFirInt8."""
+    if x.dtype not in (torch.complex64, torch.int8):
+        raise TypeError(f"input: expected complex64 or int8 I/Q, got {x.dtype}")
+    _require(x, x.dtype, "input")
+    _require(taps, torch.float32, "taps")
+    T = taps.numel()
+    L = _nsamp(x)
+    if num_outputs is None:
+        num_outputs = (L - T) // decimation + 1 if L >= T else 0
+    if num_outputs > 0:
+        _require_samples(x, x.dtype, "input", (num_outputs - 1) * decimation + T)
+    if out is None:
+        out = torch.empty(num_outputs, dtype=torch.complex64, device=x.device)
+    _require(out, torch.complex64, "output", num_outputs)
+    name = "gsdrxXlatingFirInt8" if x.dtype == torch.int8 else "gsdrxXlatingFir"
+    check(name, getattr(lib, name)(rf_sample_rate, tuning_frequency, channel_frequency, decimation,
+                                   first_sample_index, _ptr(taps), T, _ptr(x), _ptr(out), num_outputs,
+                                   _dev(x), stream_of(x)))
+    return out
+
+
+def _multi(name, x, taps, fs, tune, chans, devs, decimation, first_sample_index, num_outputs, fm,
+           odt=torch.float32):
     import ctypes
 
     if x.dtype not in (torch.complex64, torch.int8):
@@ -166,7 +191,7 @@ def _multi(name, x, taps, fs, tune, chans, devs, decimation, first_sample_index,
     if num_outputs > 0:
         _require_samples(x, x.dtype, "input", need)
     C = len(chans)
-    out = torch.empty((C, num_outputs), dtype=torch.float32, device=x.device)
+    out = torch.empty((C, num_outputs), dtype=odt, device=x.device)
     fa = (ctypes.c_float * max(C, 1))(*chans)
     args = [fs, tune, fa]
     if fm:
@@ -189,6 +214,13 @@ def am_demod_multi(x, taps, rf_sample_rate, tuning_frequency, channel_frequencie
     """gsdrxAmDemodMulti: out[c] = gsdrAmDemod with channel_frequencies[c]."""
     return _multi("gsdrxAmDemodMulti", x, taps, rf_sample_rate, tuning_frequency, channel_frequencies, None,
                   decimation, first_sample_index, num_outputs, False)
+
+
+def xlating_fir_multi(x, taps, rf_sample_rate, tuning_frequency, channel_frequencies, decimation,
+                      first_sample_index=0, num_outputs=None):
+    """gsdrxXlatingFirMulti: out[c] = gsdrxXlatingFir with channel_frequencies[c] (complex64 rows)."""
+    return _multi("gsdrxXlatingFirMulti", x, taps, rf_sample_rate, tuning_frequency, channel_frequencies, None,
+                  decimation, first_sample_index, num_outputs, False, torch.complex64)
 
 
 def quad_fm_demod(x, gain, num_outputs=None, out=None):

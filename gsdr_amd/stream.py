@@ -5,8 +5,8 @@
     for chunk in chunks:            # complex64 (or int8 I/Q) device tensors of any length
         audio = s.process(chunk)    # every output that became computable, in order
 
-Concatenated over the calls, the outputs equal one gsdrFirFC / gsdrFmDemod / gsdrAmDemod call over
-the concatenated input, bit for bit.
+Concatenated over the calls, the outputs equal one gsdrFirFC / gsdrFmDemod / gsdrAmDemod / gsdrxXlatingFir
+(kind "xlate": complex64 outputs) call over the concatenated input, bit for bit.
 
 A list of channel frequencies (and, for FM, of deviations) makes a multi-channel stream
 (gsdrxStreamCreateMulti): process() then returns a (channels, outputs) tensor whose row c is the
@@ -21,7 +21,7 @@ import torch
 from .abi import GsdrError, check, lib
 from .ops import stream_of
 
-KINDS = {"fir": 0, "fm": 1, "am": 2}
+KINDS = {"fir": 0, "fm": 1, "am": 2, "xlate": 4}  # (3 is unassigned, stream.h)
 
 
 class Stream:
@@ -63,7 +63,7 @@ class Stream:
             raise TypeError(f"input must be a contiguous {want} tensor on {self.device}")
         n_in = x.numel() // 2 if self.int8 else x.numel()
         n_out = self.outputs_for(n_in)
-        odt = torch.complex64 if self.kind == "fir" else torch.float32
+        odt = torch.complex64 if self.kind in ("fir", "xlate") else torch.float32
         if self.channels is not None:  # (channels, capacity) rows; the library writes row c at c * capacity
             if out is None:
                 out = torch.empty((self.channels, n_out), dtype=odt, device=self.device)

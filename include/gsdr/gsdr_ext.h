@@ -194,6 +194,79 @@ GSDR_C_LINKAGE GSDR_PUBLIC hipError_t gsdrxAmDemodMulti(
     hipStream_t cudaStream) GSDR_NO_EXCEPT;
 
 /*
+ * Frequency-translating FIR: the tuned, filtered, decimated COMPLEX baseband signal -- the FIR stage of
+ * gsdrAmDemod with the NCO's absolute phase kept -- for callers that bring their own demodulator (gsdrQuadFmDemod,
+ * gsdrQpskDemodulate, gsdrIirCC, a second filter, SSB ...). With inc = gsdrNcoPhaseIncrement(rfSampleRate,
+ * tuningFrequency, channelFrequency), for m in [0, numOutputs):
+ *     z[n]      = input[n] * exp(+j 2 pi ((uint32)((firstSampleIndex + n) * inc)) / 2^32)
+ *     output[m] = sum_{i < numTaps} taps[i] * z[m * decimation + i]
+ * One pass over the input: the mixed samples exist only on chip. The call reads
+ * (numOutputs - 1) * decimation + numTaps input samples, as gsdrAmDemod does; the taps are real.
+ * A stream cut into calls by hand (call k given firstSampleIndex advanced by its first output's
+ * index * decimation) reproduces one call bit for bit, at every decimation; so do gsdrxStream
+ * (GSDRX_STREAM_XLATE, stream.h) and gsdrxXlatingFirMulti.
+ * numOutputs == 0 returns hipSuccess with nothing launched. hipErrorInvalidValue, before any device call, for
+ * decimation == 0, a null input or output, null taps with numTaps > 0, rfSampleRate that is not positive and
+ * finite, or a non-finite tuningFrequency - channelFrequency. numTaps == 0 writes zeros.
+ */
+GSDR_C_LINKAGE GSDR_PUBLIC hipError_t gsdrxXlatingFir(
+    float rfSampleRate,
+    float tuningFrequency,
+    float channelFrequency,
+    uint32_t decimation,
+    size_t firstSampleIndex,
+    const float* taps,
+    size_t numTaps,
+    const hipFloatComplex* input,
+    hipFloatComplex* output,
+    size_t numOutputs,
+    int32_t cudaDevice,
+    hipStream_t cudaStream) GSDR_NO_EXCEPT;
+
+/**
+ * gsdrxXlatingFir on int8 I/Q input (interleaved, converted as gsdrInt8ToNormFloat while the tile is staged). At
+ * every decimation, 4 included, this runs the float kernels' tiles (no matrix-core form), so the output is
+ * bit-identical to gsdrInt8ToNormFloat followed by gsdrxXlatingFir with the same arguments.
+ */
+GSDR_C_LINKAGE GSDR_PUBLIC hipError_t gsdrxXlatingFirInt8(
+    float rfSampleRate,
+    float tuningFrequency,
+    float channelFrequency,
+    uint32_t decimation,
+    size_t firstSampleIndex,
+    const float* taps,
+    size_t numTaps,
+    const int8_t* input,
+    hipFloatComplex* output,
+    size_t numOutputs,
+    int32_t cudaDevice,
+    hipStream_t cudaStream) GSDR_NO_EXCEPT;
+
+/**
+ * gsdrxXlatingFir for numChannels channels of one RF input (the shape of gsdrxAmDemodMulti): channel c writes
+ * output[c * numOutputs + m], bit-identical to gsdrxXlatingFir / gsdrxXlatingFirInt8 called with
+ * channelFrequencies[c]. Decimation 2, 4 and 8 read each input tile from HBM once for up to 16 channels; other
+ * shapes run the channels one after another. channelFrequencies is a host array. numChannels == 0 or
+ * numOutputs == 0 return hipSuccess with nothing launched; a null channelFrequencies or an unknown sampleFormat
+ * return hipErrorInvalidValue, as do the cases listed for gsdrxXlatingFir.
+ */
+GSDR_C_LINKAGE GSDR_PUBLIC hipError_t gsdrxXlatingFirMulti(
+    float rfSampleRate,
+    float tuningFrequency,
+    const float* channelFrequencies,
+    uint32_t numChannels,
+    uint32_t decimation,
+    size_t firstSampleIndex,
+    const float* taps,
+    size_t numTaps,
+    int sampleFormat,
+    const void* input,
+    hipFloatComplex* output,
+    size_t numOutputs,
+    int32_t cudaDevice,
+    hipStream_t cudaStream) GSDR_NO_EXCEPT;
+
+/*
  * Config 5's channel model (BASELINE configs[4]: QPSK256 modulate -> AWGN -> demod): the output of
  * gsdrQpsk256Modulate (the table set by gsdrQpsk256InitConstellation for constellationType) plus
  * additive white Gaussian noise of standard deviation `sigma` per axis, in one pass:

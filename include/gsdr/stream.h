@@ -19,7 +19,9 @@
  * where a call or tile starts, and the NCO phase is a function of the absolute sample index). Output m is produced by the first call after which its
  * whole window has arrived: FIR/AM windows are taps samples, FM windows taps + decimation samples.
  *
- * Kinds: GSDRX_STREAM_FIR (gsdrFirFC), GSDRX_STREAM_FM (gsdrFmDemod), GSDRX_STREAM_AM (gsdrAmDemod).
+ * Kinds: GSDRX_STREAM_FIR (gsdrFirFC), GSDRX_STREAM_FM (gsdrFmDemod), GSDRX_STREAM_AM (gsdrAmDemod),
+ * GSDRX_STREAM_XLATE (gsdrxXlatingFir: the tuned, filtered, decimated complex baseband signal; windows of taps
+ * samples as for AM, hipFloatComplex outputs).
  * Sample formats: GSDRX_SAMPLES_CF32 (hipFloatComplex) or GSDRX_SAMPLES_CS8 (interleaved int8 I/Q,
  * the gsdrx*Int8 entry points of gsdr_ext.h). int8 streams reproduce those entry points' defaults, the
  * decimation-4 matrix-core kernels included: their summation blocks follow the absolute output index
@@ -46,13 +48,15 @@
 #define GSDRX_STREAM_FIR 0
 #define GSDRX_STREAM_FM 1
 #define GSDRX_STREAM_AM 2
+/* (3 is unassigned and stays an invalid kind) */
+#define GSDRX_STREAM_XLATE 4
 
 typedef struct gsdrxStream_t* gsdrxStream;
 
 /**
  * Create a stream on `cudaDevice` (allocates two history buffers and a seam buffer of at most
  * 2 * (tapCount + decimation) samples each; nothing is allocated later). For GSDRX_STREAM_FIR the
- * frequency arguments are ignored; for GSDRX_STREAM_AM frequencyDeviation is ignored.
+ * frequency arguments are ignored; for GSDRX_STREAM_AM and GSDRX_STREAM_XLATE frequencyDeviation is ignored.
  * Returns hipErrorInvalidValue for a null handle pointer, decimation == 0, tapCount == 0, null taps
  * or an unknown kind / sample format.
  */
@@ -71,16 +75,17 @@ GSDR_C_LINKAGE GSDR_PUBLIC hipError_t gsdrxStreamCreate(
     int32_t cudaDevice) GSDR_NO_EXCEPT;
 
 /**
- * Create a MULTI-CHANNEL stream: `numChannels` FM or AM channels of one RF input (the streaming form of
- * gsdrxFmDemodMulti / gsdrxAmDemodMulti; the intent of the reference's dead k_Fm4x, src/fm.cu:71-179).
- * Channel c mixes by tuningFrequency - channelFrequencies[c] and, for FM, uses frequencyDeviations[c]
- * (ignored, and may be null, for AM). The input history is kept once for all channels. Each
+ * Create a MULTI-CHANNEL stream: `numChannels` FM, AM or XLATE channels of one RF input (the streaming form of
+ * gsdrxFmDemodMulti / gsdrxAmDemodMulti / gsdrxXlatingFirMulti; the intent of the reference's dead k_Fm4x,
+ * src/fm.cu:71-179). Channel c mixes by tuningFrequency - channelFrequencies[c] and, for FM, uses
+ * frequencyDeviations[c] (ignored, and may be null, for AM and XLATE). The input history is kept once for all channels. Each
  * gsdrxStreamProcess call is one launch per 16 channels for complex float input at decimation 2, 4 or 8
  * (the grouped kernel: each input tile read from HBM about once for all its channels), one launch per channel
  * otherwise (int8 I/Q at decimation 4: the matrix-core chain of each channel). Channel c's outputs are
  * bit-identical to a single-channel gsdrxStream with that channel's frequency (and so to one monolithic
- * gsdrFmDemod / gsdrAmDemod / gsdrx*Int8 call). In gsdrxStreamProcess, channel c's outputs go to
- * output + c * outputCapacity (outputCapacity = the per-channel capacity, in outputs), and
+ * gsdrFmDemod / gsdrAmDemod / gsdrxXlatingFir / gsdrx*Int8 call). In gsdrxStreamProcess, channel c's outputs go to
+ * output + c * outputCapacity (outputCapacity = the per-channel capacity, in outputs: floats for FM and AM,
+ * complex elements for XLATE), and
  * *numOutputsWritten / gsdrxStreamOutputsFor count the outputs of ONE channel.
  * Returns hipErrorInvalidValue for kind GSDRX_STREAM_FIR, numChannels == 0, null channelFrequencies, null
  * frequencyDeviations for FM, and as gsdrxStreamCreate.
@@ -105,7 +110,7 @@ GSDR_C_LINKAGE GSDR_PUBLIC size_t gsdrxStreamOutputsFor(gsdrxStream stream, size
 
 /**
  * Append `numInputSamples` samples (device memory, in the stream's sample format) and write every
- * output that became computable to `output` (hipFloatComplex for FIR, float for FM/AM), in order
+ * output that became computable to `output` (hipFloatComplex for FIR and XLATE, float for FM/AM), in order
  * (a multi-channel stream: channel c's at output + c * outputCapacity).
  * `*numOutputsWritten` receives the count (host-known, no synchronisation). Asynchronous on
  * `cudaStream`; the input chunk may be reused once the stream's work has completed. Returns
