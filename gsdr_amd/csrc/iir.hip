@@ -15,7 +15,7 @@
 //      whose last lane is the group aggregate for the next level; down-sweep = every element's start
 //      state M^r S_group + prefix_(r-1) at once (table of M^r, r < 64, per level).
 //   3. k_iir_chunks<kFinal>: each chunk re-runs from its true start state and writes y.
-//   4. k_iir_history: the caller's history buffers receive the last P inputs / outputs.
+//   4. The last chunk of that pass writes the last P inputs / outputs into the caller's history buffers.
 // For P <= 8 level 0's up-sweep runs inside the tails pass and its down-sweep in the final pass; up to
 // 2^25 samples the levels above 1 and level 1's down-sweep take one launch (k_iir_scan_upper), so 2^24
 // samples run as tails, level-1 up-sweep, upper scan, final: 4 launches.
@@ -24,18 +24,14 @@
 // coefficients beyond K-1 leave the recursion unchanged).
 #include <hip/hip_runtime.h>
 
-
 #include <algorithm>
 
 #include "gsdr/iir.h"
+#include "iir_plan.hpp"
 #include "launch.hpp"
 
 namespace gsdr {
 namespace iir {
-
-constexpr int kChunk = 32;  // samples per level-0 chunk (>= the largest P)
-constexpr int kGroup = 64;  // scan elements per group = one wave, one element per lane
-constexpr int kMaxLevels = 8;
 
 // The recursion state, the scan and the transition matrices are kept in double: the direct form
 // amplifies an inconsistent perturbation of its P-sample state by 10^2..10^3 (tests/test_gpu_iir.py),
@@ -51,6 +47,8 @@ template <>
 struct Acc<float2> {
   using type = double2;
 };
+template <class S>
+using AccT = typename Acc<S>::type;
 
 __device__ __forceinline__ float zero_s(float) { return 0.0f; }
 __device__ __forceinline__ float2 zero_s(float2) { return make_float2(0.0f, 0.0f); }
@@ -66,8 +64,6 @@ __device__ __forceinline__ double2 fma_s(double c, float2 x, double2 acc) {
 }
 __device__ __forceinline__ double to_acc(float v) { return (double)v; }
 __device__ __forceinline__ double2 to_acc(float2 v) { return make_double2(v.x, v.y); }
-__device__ __forceinline__ float to_sample(double v) { return (float)v; }
-__device__ __forceinline__ float2 to_sample(double2 v) { return make_float2((float)v.x, (float)v.y); }
 __device__ __forceinline__ double add_s(double a, double b) { return a + b; }
 __device__ __forceinline__ double shfl_up_s(double v, int d) { return __shfl_up(v, d, 64); }
 __device__ __forceinline__ double2 shfl_up_s(double2 v, int d) {
@@ -93,8 +89,6 @@ __device__ __forceinline__ double coeff(const float* c, int K, int i) {
   return i < K ? (double)v : 0.0;
 }
 
-enum ChunkPass : int { kTails = 0, kFinal = 1 };
-
 // x[n] for n >= -P: the input, or the caller's input history (K-1 entries) for n < 0, else zero
 template <class S>
 __device__ __forceinline__ S x_at(const S* __restrict__ x, const S* __restrict__ xh, int K, int64_t n) {
@@ -116,6 +110,63 @@ __device__ __forceinline__ void mat_mul(const double* __restrict__ A, const doub
 #pragma unroll
     for (int l = 0; l < P; ++l) acc = fma(A[i * P + l], B[l * P + j], acc);
     C[e] = acc;
+  }
+}
+
+// acc += M x (M: P x P, row-major; double, or double2 = two recursions sharing M): per row i from acc[i], then
+// l = 0 .. P-1. Every scan step and every start state below is this one order of operations. mat_row_acc is one
+// row of it, for down_group, which stores each row as it is formed.
+template <class V, int P>
+__device__ __forceinline__ V mat_row_acc(const double* __restrict__ Mi, const V (&x)[P], V a) {
+#pragma unroll
+  for (int l = 0; l < P; ++l) a = fma_s(Mi[l], x[l], a);
+  return a;
+}
+template <class V, int P>
+__device__ __forceinline__ void mat_vec_acc(const double* __restrict__ M, const V (&x)[P], V (&acc)[P]) {
+#pragma unroll
+  for (int i = 0; i < P; ++i) acc[i] = mat_row_acc<V, P>(M + i * P, x, acc[i]);
+}
+
+// Hillis-Steele scan of one group over the affine composition from zero state, one element per lane:
+// v_r <- v_r + M^(2^s) v_(r-2^s), s < 6, ending with the zero-state prefix through element r. M^(2^s) is pw[2^s] of
+// a level's table T[r] = M^r (kTablePow) or pw[s] of powers stored one after another (kPackedPow). The steps run on
+// a copy of the caller's array: in place through the reference, k_iir_up<double, 16> took 134 VGPRs, not 70.
+constexpr bool kTablePow = false, kPackedPow = true;
+template <class V, int P, bool PACKED>
+__device__ __forceinline__ void wave_scan(V (&io)[P], int r, const double* __restrict__ pw) {
+  V v[P];
+#pragma unroll
+  for (int i = 0; i < P; ++i) v[i] = io[i];
+#pragma unroll
+  for (int s = 0; s < 6; ++s) {
+    const int d = 1 << s;
+    V w[P];
+#pragma unroll
+    for (int i = 0; i < P; ++i) w[i] = shfl_up_s(v[i], d);
+    if (r >= d) mat_vec_acc<V, P>(pw + (size_t)(PACKED ? s : d) * P * P, w, v);
+  }
+#pragma unroll
+  for (int i = 0; i < P; ++i) io[i] = v[i];
+}
+
+// Column t of M_0, the transition over one chunk: the state after kChunk steps of the homogeneous recursion
+// y[n] = -sum a[i] y[n-i] from e_t. The setup tables (iir_setup) and the fused tails pass's powers (build_pow)
+// both grow from this one function, so they hold the same doubles.
+template <int P>
+__device__ __forceinline__ void chunk_transition_column(const Coeffs& cf, int t, double (&m)[P]) {
+  double am[P + 1];
+#pragma unroll
+  for (int i = 0; i <= P; ++i) am[i] = -coeff(cf.a, cf.K, i);
+#pragma unroll
+  for (int i = 0; i < P; ++i) m[i] = i == t ? 1.0 : 0.0;
+  for (int k = 0; k < kChunk; ++k) {
+    double acc = 0.0;
+#pragma unroll
+    for (int i = 1; i <= P; ++i) acc = fma(am[i], m[i - 1], acc);
+#pragma unroll
+    for (int i = P - 1; i > 0; --i) m[i] = m[i - 1];
+    m[0] = acc;
   }
 }
 
@@ -147,23 +198,11 @@ __device__ __forceinline__ void iir_setup(const Coeffs& cf, const S* __restrict_
   for (int lv = 0; lv <= levels; ++lv) {
     double* __restrict__ W = INLDS ? work : T + (size_t)lv * kGroup * PP;
     if (lv == 0) {
-      if (t < P) {  // M_0, column t
-        double am[P + 1];
+      if (t < P) {
+        double m[P];
+        chunk_transition_column<P>(cf, t, m);
 #pragma unroll
-        for (int i = 0; i <= P; ++i) am[i] = -coeff(cf.a, cf.K, i);
-        double ys[P];
-#pragma unroll
-        for (int i = 0; i < P; ++i) ys[i] = i == t ? 1.0 : 0.0;
-        for (int k = 0; k < kChunk; ++k) {
-          double acc = 0.0;
-#pragma unroll
-          for (int i = 1; i <= P; ++i) acc = fma(am[i], ys[i - 1], acc);
-#pragma unroll
-          for (int i = P - 1; i > 0; --i) ys[i] = ys[i - 1];
-          ys[0] = acc;
-        }
-#pragma unroll
-        for (int i = 0; i < P; ++i) W[PP + i * P + t] = ys[i];
+        for (int i = 0; i < P; ++i) W[PP + i * P + t] = m[i];
       }
     } else {  // M_lv = M_{lv-1}^64 = (M_{lv-1}^32)^2, from the previous level's table
       const double* Tp = INLDS ? work : T + (size_t)(lv - 1) * kGroup * PP;
@@ -214,17 +253,55 @@ struct TileShape {
   static constexpr int NC = sizeof(S) / sizeof(float);  // components per sample: one lane each
   static constexpr int CPW = WG / NC;                     // chunks per workgroup
   static constexpr int TS = CPW * kChunk;                 // samples per tile: 33 KB of LDS either way
+  static_assert(TS * sizeof(S) == kTileSampleBytes, "the plan counts these tiles");
   static constexpr int STRIDE = kChunk + 1;
   __device__ static int at(int idx) { return idx + idx / kChunk; }
 };
 
-struct SetupArgs {
-  const void* yh;
-  void* s0;
+enum ChunkPass : int { kTails = 0, kFinal = 1 };
+
+// What each pass of k_iir_chunks reads besides the input, by pass and by whether level 0 of the scan is fused
+// into the chunk passes. Scan states are AccT<S>, P per element.
+template <class S, int PASS, bool FUSED>
+struct PassArgs;
+template <class S>
+struct SetupArgs {  // the setup workgroup of the tails pass (iir_setup)
+  const S* yh;
+  AccT<S>* s0;
   double* T;
   int levels;
-  const void* xh;  // the caller's input history, copied to xh_copy for the final pass
-  void* xh_copy;
+  const S* xh;  // the caller's input history, copied to xh_copy for the final pass
+  S* xh_copy;
+};
+template <class S>
+struct PassArgs<S, kTails, false> {
+  SetupArgs<S> setup;
+  AccT<S>* tails;  // every chunk's zero-state tail (the level-0 elements)
+};
+template <class S>
+struct PassArgs<S, kTails, true> {
+  SetupArgs<S> setup;
+  AccT<S>* incl;  // level-0 inclusive zero-state prefixes, written by the pass's own up-sweep
+  AccT<S>* aggs;  // level-1 elements (group aggregates), or null when level 0 is the top
+};
+// final pass: its last chunk writes the caller's history buffers (Pk = K - 1 entries); the pass reads the input
+// history from the tails pass's copy, so no tile reads what the last one overwrites
+template <class S>
+struct PassArgs<S, kFinal, false> {
+  S* y;
+  const AccT<S>* starts;  // every chunk's start state
+  float *xh_out, *yh_out;
+  int Pk;
+};
+template <class S>
+struct PassArgs<S, kFinal, true> {
+  S* y;
+  const AccT<S>* incl;    // level-0 inclusive prefixes (from the tails pass)
+  const double* T0;       // M_0^r, r < 64
+  const AccT<S>* gstart;  // level-1 start states, or null: s0 is the group start
+  const AccT<S>* s0;
+  float *xh_out, *yh_out;
+  int Pk;
 };
 
 template <int P>
@@ -251,47 +328,18 @@ constexpr int kFusedMaxP = IIR_FUSED_MAXP;
 #error "IIR_PROBE_TAILS / IIR_PROBE_FINAL produce wrong results (timing ablations): probe builds only"
 #endif
 
-struct ScanArgs {
-  double* incl;          // level-0 inclusive zero-state prefixes (A[P] per chunk); tails pass writes
-  double* aggs;          // level-1 elements (group aggregates), or null when level 0 is the top
-  const double* T0;      // M_0^r, r < 64 (final pass)
-  const double* gstart;  // level-1 start states (final pass), or null: s0 is the group start
-  const double* s0;
-  // final pass: the caller's history buffers, written by the last chunk (the pass reads the input history
-  // from the tails pass's copy, so no tile reads what the last one overwrites); Pk = K - 1 entries
-  float* xh_out;
-  float* yh_out;
-  int Pk;
-};
-
-// Up-sweep of one level-0 group from the workgroup's tails in LDS (loc = the group's 64 elements),
-// with the powers M_0^(2^s) in pw[s]: as up_group, same operations.
-template <class A, int P>
-__device__ __forceinline__ void up_group_fused(const A* __restrict__ loc, uint64_t E, const double* __restrict__ pw,
-                                               A* __restrict__ incl, A* __restrict__ aggs, uint64_t g, int r) {
-  constexpr int PP = P * P;
+// Up-sweep of group g of one level (one wave, lane r = element j = g*64 + r, read from mine[0 .. P): the level's
+// elements in global memory, or the workgroup's tails in LDS for the fused level 0). Lane r's result, the zero-state
+// prefix through element r, is kept in `incl` for the down-sweep; the last lane's is the next level's element g.
+template <class A, int P, bool PACKED>
+__device__ __forceinline__ void up_group(const A* __restrict__ mine, uint64_t E, const double* __restrict__ pw,
+                                         A* __restrict__ incl, A* __restrict__ aggs, uint64_t g, int r) {
   const uint64_t j = g * kGroup + r;
   const uint64_t last = (E - 1 < g * kGroup + kGroup - 1) ? E - 1 - g * kGroup : kGroup - 1;
   A v[P];
 #pragma unroll
-  for (int i = 0; i < P; ++i) v[i] = j < E ? loc[r * P + i] : zero_s(A{});
-#pragma unroll
-  for (int s = 0; s < 6; ++s) {
-    const int d = 1 << s;
-    const double* __restrict__ Md = pw + s * PP;
-    A w[P];
-#pragma unroll
-    for (int i = 0; i < P; ++i) w[i] = shfl_up_s(v[i], d);
-    if (r >= d) {
-#pragma unroll
-      for (int i = 0; i < P; ++i) {
-        A acc = v[i];
-#pragma unroll
-        for (int l = 0; l < P; ++l) acc = fma_s(Md[i * P + l], w[l], acc);
-        v[i] = acc;
-      }
-    }
-  }
+  for (int i = 0; i < P; ++i) v[i] = j < E ? mine[i] : zero_s(A{});
+  wave_scan<A, P, PACKED>(v, r, pw);
   if (j < E) {
 #pragma unroll
     for (int i = 0; i < P; ++i) incl[j * P + i] = v[i];
@@ -305,9 +353,7 @@ __device__ __forceinline__ void up_group_fused(const A* __restrict__ loc, uint64
 template <class S, int P, int PASS, bool VEC, bool FUSED = false>
 __global__ __launch_bounds__(TileShape<S>::WG) void k_iir_chunks(Coeffs cf, const S* __restrict__ x,
                                                                  const S* __restrict__ xh, uint64_t n,
-                                                                 const typename Acc<S>::type* __restrict__ starts,
-                                                                 typename Acc<S>::type* __restrict__ tails,
-                                                                 S* __restrict__ y, SetupArgs setup, ScanArgs sc) {
+                                                                 PassArgs<S, PASS, FUSED> pa) {
   using TSh = TileShape<S>;
   using A = typename Acc<S>::type;
   constexpr size_t kTileBytes = sizeof(S) * TSh::CPW * TSh::STRIDE;
@@ -325,9 +371,9 @@ __global__ __launch_bounds__(TileShape<S>::WG) void k_iir_chunks(Coeffs cf, cons
     // the extra FIRST workgroup builds the scan constants while the others compute the tails (as the
     // last one it was dispatched after most tiles and finished after them: ~7 us at the kernel's end)
     if (blockIdx.x == 0) {
-      if (setup.xh != nullptr && t < cf.K - 1) static_cast<S*>(setup.xh_copy)[t] = static_cast<const S*>(setup.xh)[t];
-      iir_setup<S, P, TSh::WG, kTableInLds<P>>(cf, static_cast<const S*>(setup.yh), static_cast<A*>(setup.s0), setup.T,
-                                               setup.levels, reinterpret_cast<double*>(smem));
+      const SetupArgs<S>& su = pa.setup;
+      if (su.xh != nullptr && t < cf.K - 1) su.xh_copy[t] = su.xh[t];
+      iir_setup<S, P, TSh::WG, kTableInLds<P>>(cf, su.yh, su.s0, su.T, su.levels, reinterpret_cast<double*>(smem));
       return;
     }
   }
@@ -347,23 +393,11 @@ __global__ __launch_bounds__(TileShape<S>::WG) void k_iir_chunks(Coeffs cf, cons
   uint64_t ti = PASS == kTails ? blockIdx.x - 1 : blockIdx.x;
   const uint64_t first_ti = ti;
   auto build_pow = [&]() {
-    // M_0 (column j = state after kChunk steps of the homogeneous recursion from e_j), then squared:
-    // the same operations as iir_setup's T[1], T[2], ..., T[32], so the same doubles
+    // M_0 (chunk_transition_column, as iir_setup's T[1]), then squared five times: the same products as
+    // iir_setup's T[2], T[4], ..., T[32], so the same doubles
     if (t < P) {
-      double am[P + 1];
-#pragma unroll
-      for (int i = 0; i <= P; ++i) am[i] = -coeff(cf.a, cf.K, i);
       double m[P];
-#pragma unroll
-      for (int i = 0; i < P; ++i) m[i] = i == t ? 1.0 : 0.0;
-      for (int k = 0; k < kChunk; ++k) {
-        double acc = 0.0;
-#pragma unroll
-        for (int i = 1; i <= P; ++i) acc = fma(am[i], m[i - 1], acc);
-#pragma unroll
-        for (int i = P - 1; i > 0; --i) m[i] = m[i - 1];
-        m[0] = acc;
-      }
+      chunk_transition_column<P>(cf, t, m);
 #pragma unroll
       for (int i = 0; i < P; ++i) mpow[i * P + t] = m[i];
     }
@@ -379,7 +413,6 @@ __global__ __launch_bounds__(TileShape<S>::WG) void k_iir_chunks(Coeffs cf, cons
     b[i] = coeff(cf.b, cf.K, i);
     am[i] = -coeff(cf.a, cf.K, i);
   }
-  double* __restrict__ tails_d = reinterpret_cast<double*>(tails);
   // One tile per workgroup (the launcher starts ntiles workgroups): written as a loop that ends after its
   // first pass, so nothing is live across iterations. With `ti += nwg` the compiler kept the coefficients
   // and the fused scan's state live around the loop: 148 VGPRs, 3 waves per SIMD, instead of 66 / 112.
@@ -403,12 +436,13 @@ __global__ __launch_bounds__(TileShape<S>::WG) void k_iir_chunks(Coeffs cf, cons
     if constexpr (kPro) {
       // level-0 down-sweep for this chunk: start = M_0^r S_g + prefix_(r-1) (as down_group)
       if (n0 < n) {
-        const double* __restrict__ Mr = sc.T0 + (size_t)r * PP;
+        const double* __restrict__ Mr = pa.T0 + (size_t)r * PP;
 #pragma unroll
         for (int e = 0; e < PP; ++e) mr[e] = Mr[e];
+        const double* __restrict__ incl_d = reinterpret_cast<const double*>(pa.incl);
 #pragma unroll
-        for (int i = 0; i < P; ++i) inc[i] = r > 0 ? sc.incl[((c - 1) * P + i) * NC + comp] : 0.0;
-        const double* __restrict__ sg = sc.gstart ? sc.gstart + g * P * NC : sc.s0;
+        for (int i = 0; i < P; ++i) inc[i] = r > 0 ? incl_d[((c - 1) * P + i) * NC + comp] : 0.0;
+        const double* __restrict__ sg = reinterpret_cast<const double*>(pa.gstart ? pa.gstart + g * P : pa.s0);
 #pragma unroll
         for (int l = 0; l < P; ++l) sgc[l] = sg[l * NC + comp];
       }
@@ -422,16 +456,12 @@ __global__ __launch_bounds__(TileShape<S>::WG) void k_iir_chunks(Coeffs cf, cons
     if constexpr (kPro) {
       if (n0 < n) {
 #pragma unroll
-        for (int i = 0; i < P; ++i) {
-          double acc = inc[i];
-#pragma unroll
-          for (int l = 0; l < P; ++l) acc = fma(mr[i * P + l], sgc[l], acc);
-          ys[i] = acc;
-        }
+        for (int i = 0; i < P; ++i) ys[i] = inc[i];
+        mat_vec_acc<double, P>(mr, sgc, ys);
       }
     } else if constexpr (PASS == kFinal && !FUSED) {
       if (n0 < n) {
-        const double* __restrict__ starts_d = reinterpret_cast<const double*>(starts);
+        const double* __restrict__ starts_d = reinterpret_cast<const double*>(pa.starts);
 #pragma unroll
         for (int i = 0; i < P; ++i) ys[i] = starts_d[(c * P + i) * NC + comp];
       }
@@ -496,6 +526,7 @@ __global__ __launch_bounds__(TileShape<S>::WG) void k_iir_chunks(Coeffs cf, cons
         for (uint32_t k = 0; k < len; ++k) step(k);
       }
       if constexpr (PASS == kTails && !FUSED) {
+        double* __restrict__ tails_d = reinterpret_cast<double*>(pa.tails);
 #pragma unroll
         for (int i = 0; i < P; ++i) tails_d[(c * P + i) * NC + comp] = ys[i];
       } else if constexpr (PASS == kFinal) {
@@ -504,9 +535,9 @@ __global__ __launch_bounds__(TileShape<S>::WG) void k_iir_chunks(Coeffs cf, cons
           // history buffers (component comp of entry i)
 #pragma unroll
           for (int i = 0; i < P; ++i) {
-            if (i < sc.Pk) {
-              if (sc.yh_out) sc.yh_out[i * NC + comp] = (float)ys[i];
-              if (sc.xh_out) sc.xh_out[i * NC + comp] = (float)xd[i];
+            if (i < pa.Pk) {
+              if (pa.yh_out) pa.yh_out[i * NC + comp] = (float)ys[i];
+              if (pa.xh_out) pa.xh_out[i * NC + comp] = (float)xd[i];
             }
           }
         }
@@ -524,12 +555,13 @@ __global__ __launch_bounds__(TileShape<S>::WG) void k_iir_chunks(Coeffs cf, cons
       if (!(IIR_PROBE_TAILS & 2) && w < TSh::CPW / kGroup) {
         const uint64_t C = (n + kChunk - 1) / kChunk;
         const uint64_t g = ti * (TSh::CPW / kGroup) + w;
-        up_group_fused<A, P>(tl + w * kGroup * P, C, mpow, reinterpret_cast<A*>(sc.incl),
-                             reinterpret_cast<A*>(sc.aggs), g, t % kGroup);
+        const int lane = t % kGroup;
+        up_group<A, P, kPackedPow>(tl + (w * kGroup + lane) * P, C, mpow, pa.incl, pa.aggs, g, lane);
       }
     }
     if constexpr (PASS == kFinal) {
       lds_barrier();
+      S* __restrict__ y = pa.y;
       if (whole) {
         float4* __restrict__ dst = reinterpret_cast<float4*>(y + base);
 #pragma unroll
@@ -543,46 +575,6 @@ __global__ __launch_bounds__(TileShape<S>::WG) void k_iir_chunks(Coeffs cf, cons
       }
     }
     lds_barrier();  // the tile's LDS is free for the next one
-  }
-}
-
-// Up-sweep of group g of one level (one wave, lane r = element g*64 + r): Hillis-Steele over the
-// affine composition from zero state, v_r <- v_r + M^(2^s) v_(r-2^s). Lane r's result is the
-// zero-state prefix through element r (kept in `incl` for the down-sweep); the group's last lane holds
-// the group aggregate for the next level.
-template <class A, int P>
-__device__ __forceinline__ void up_group(const A* __restrict__ elems, uint64_t E, const double* __restrict__ T,
-                                         A* __restrict__ incl, A* __restrict__ aggs, uint64_t g, int r) {
-  constexpr int PP = P * P;
-  const uint64_t j = g * kGroup + r;
-  const uint64_t last = (E - 1 < g * kGroup + kGroup - 1) ? E - 1 - g * kGroup : kGroup - 1;
-  A v[P];
-#pragma unroll
-  for (int i = 0; i < P; ++i) v[i] = j < E ? elems[j * P + i] : zero_s(A{});
-#pragma unroll
-  for (int s = 0; s < 6; ++s) {
-    const int d = 1 << s;
-    const double* __restrict__ Md = T + (size_t)d * PP;
-    A w[P];
-#pragma unroll
-    for (int i = 0; i < P; ++i) w[i] = shfl_up_s(v[i], d);
-    if (r >= d) {
-#pragma unroll
-      for (int i = 0; i < P; ++i) {
-        A acc = v[i];
-#pragma unroll
-        for (int l = 0; l < P; ++l) acc = fma_s(Md[i * P + l], w[l], acc);
-        v[i] = acc;
-      }
-    }
-  }
-  if (j < E) {
-#pragma unroll
-    for (int i = 0; i < P; ++i) incl[j * P + i] = v[i];
-  }
-  if (aggs && (uint64_t)r == last) {
-#pragma unroll
-    for (int i = 0; i < P; ++i) aggs[g * P + i] = v[i];
   }
 }
 
@@ -605,10 +597,7 @@ __device__ __forceinline__ void down_group(uint64_t E, const double* __restrict_
     const double* __restrict__ Mr = T + (size_t)r * PP;
 #pragma unroll
     for (int i = 0; i < P; ++i) {
-      A acc = r > 0 ? pre[i] : zero_s(A{});
-#pragma unroll
-      for (int l = 0; l < P; ++l) acc = fma_s(Mr[i * P + l], sg[l], acc);
-      incl_starts[j * P + i] = acc;
+      incl_starts[j * P + i] = mat_row_acc<A, P>(Mr + i * P, sg, r > 0 ? pre[i] : zero_s(A{}));
     }
   }
 }
@@ -617,7 +606,8 @@ __device__ __forceinline__ void down_group(uint64_t E, const double* __restrict_
 template <class A, int P>
 __global__ __launch_bounds__(64) void k_iir_up(const A* __restrict__ elems, uint64_t E, const double* __restrict__ T,
                                                A* __restrict__ incl, A* __restrict__ aggs) {
-  up_group<A, P>(elems, E, T, incl, aggs, blockIdx.x, threadIdx.x);
+  up_group<A, P, kTablePow>(elems + ((uint64_t)blockIdx.x * kGroup + threadIdx.x) * P, E, T, incl, aggs, blockIdx.x,
+                           threadIdx.x);
 }
 
 template <class A, int P>
@@ -633,30 +623,33 @@ __global__ __launch_bounds__(64) void k_iir_down(uint64_t E, const double* __res
 // loads issued together) the whole of levels 1..3 for 2^24 samples took 72 us on one CU against ~19 us
 // for the per-level launches. Up and down in one launch: 8.9 us instead of 6.2 + 4.9 us.
 constexpr int kRestWaves = 16;
-constexpr int kRestGroups = 16;
+// a call's planned workspace, typed: level k's elements, their start states and its table T[r] = M_k^r
 template <class A>
-struct Levels {
-  A* elems[kMaxLevels + 1];
-  A* starts[kMaxLevels + 1];
-  const double* T[kMaxLevels + 1];
-  uint64_t E[kMaxLevels + 1];
-  int levels;
+struct Workspace {
+  char* ws;
+  ScanPlan pl;
+  __host__ __device__ A* elems(int k) const { return reinterpret_cast<A*>(ws + pl.elems[k]); }
+  __host__ __device__ A* starts(int k) const { return reinterpret_cast<A*>(ws + pl.starts[k]); }
+  __host__ __device__ double* table(int k) const {
+    return reinterpret_cast<double*>(ws + pl.tables + k * pl.table_bytes);
+  }
 };
 
 template <class A, int P>
-__global__ __launch_bounds__(64 * kRestWaves) void k_iir_scan_rest(Levels<A> L, const A* __restrict__ s0, int first) {
+__global__ __launch_bounds__(64 * kRestWaves) void k_iir_scan_rest(Workspace<A> W, const A* __restrict__ s0, int from) {
   const int w = threadIdx.x / 64, r = threadIdx.x % 64;
-  for (int k = first; k <= L.levels; ++k) {
-    const uint64_t groups = ceil_div<uint64_t>(L.E[k], kGroup);
+  for (int k = from; k <= W.pl.levels; ++k) {
+    const uint64_t groups = ceil_div<uint64_t>(W.pl.E[k], kGroup);
     for (uint64_t g = w; g < groups; g += kRestWaves) {
-      up_group<A, P>(L.elems[k], L.E[k], L.T[k], L.starts[k], k < L.levels ? L.elems[k + 1] : nullptr, g, r);
+      up_group<A, P, kTablePow>(W.elems(k) + (g * kGroup + r) * P, W.pl.E[k], W.table(k), W.starts(k),
+                                k < W.pl.levels ? W.elems(k + 1) : nullptr, g, r);
     }
     __syncthreads();
   }
-  for (int k = L.levels; k >= first; --k) {
-    const uint64_t groups = ceil_div<uint64_t>(L.E[k], kGroup);
+  for (int k = W.pl.levels; k >= from; --k) {
+    const uint64_t groups = ceil_div<uint64_t>(W.pl.E[k], kGroup);
     for (uint64_t g = w; g < groups; g += kRestWaves) {
-      down_group<A, P>(L.E[k], L.T[k], k < L.levels ? L.starts[k + 1] : nullptr, s0, L.starts[k], g, r);
+      down_group<A, P>(W.pl.E[k], W.table(k), k < W.pl.levels ? W.starts(k + 1) : nullptr, s0, W.starts(k), g, r);
     }
     __syncthreads();
   }
@@ -670,18 +663,7 @@ __global__ __launch_bounds__(64 * kRestWaves) void k_iir_scan_rest(Levels<A> L, 
 // walked levels 2..3 through global memory (one dependent round trip per phase, 8.3 us at 2^24 samples) and
 // a separate level-1 down-sweep (or its fold into the final pass's prologue).
 constexpr int kUpperWaves = 4;
-constexpr uint64_t kUpperE2 = kUpperWaves * kGroup;
-
-template <int P>
-__device__ __forceinline__ void mat_vec_acc(const double* __restrict__ M, const double (&x)[P], double (&acc)[P]) {
-#pragma unroll
-  for (int i = 0; i < P; ++i) {
-    double a = acc[i];
-#pragma unroll
-    for (int l = 0; l < P; ++l) a = fma(M[i * P + l], x[l], a);
-    acc[i] = a;
-  }
-}
+static_assert(kUpperE2 == kUpperWaves * kGroup, "one wave per level-2 group");
 
 // T[k] = M_k^r, r < 64 (setup tables); elems1 = level-1 elements (their inclusive prefixes in starts1 from
 // k_iir_up, overwritten with start states), elems2 = level-2 elements (group aggregates of level 1)
@@ -712,14 +694,7 @@ __global__ __launch_bounds__(64 * kUpperWaves) void k_iir_scan_upper(uint64_t E1
   const uint64_t j2 = (uint64_t)t;
 #pragma unroll
   for (int i = 0; i < P; ++i) v[i] = j2 < E2 ? elems2[(j2 * P + i) * NC + comp] : 0.0;
-#pragma unroll
-  for (int s = 0; s < 6; ++s) {
-    const int d = 1 << s;
-    double u[P];
-#pragma unroll
-    for (int i = 0; i < P; ++i) u[i] = __shfl_up(v[i], d, 64);
-    if (r >= d) mat_vec_acc<P>(T2 + (size_t)d * PP, u, v);
-  }
+  wave_scan<double, P, kTablePow>(v, r, T2);
 #pragma unroll
   for (int i = 0; i < P; ++i) incl2[t][i] = v[i];
   __syncthreads();
@@ -735,7 +710,7 @@ __global__ __launch_bounds__(64 * kUpperWaves) void k_iir_scan_upper(uint64_t E1
         double nv[P];
 #pragma unroll
         for (int i = 0; i < P; ++i) nv[i] = incl2[q * kGroup + kGroup - 1][i];
-        mat_vec_acc<P>(T3 + PP, sg, nv);
+        mat_vec_acc<double, P>(T3 + PP, sg, nv);
 #pragma unroll
         for (int i = 0; i < P; ++i) sg[i] = nv[i];
       }
@@ -752,7 +727,7 @@ __global__ __launch_bounds__(64 * kUpperWaves) void k_iir_scan_upper(uint64_t E1
     s2[i] = r2 > 0 ? incl2[e2 - 1][i] : 0.0;
     sg[i] = gstart[q2][i];
   }
-  mat_vec_acc<P>(T2 + (size_t)r2 * PP, sg, s2);
+  mat_vec_acc<double, P>(T2 + (size_t)r2 * PP, sg, s2);
   // 4. level-1 down-sweep of group e2: element e1 starts in M_1^r S2 + incl1[e1 - 1]
   double st[P];
 #pragma unroll
@@ -760,7 +735,7 @@ __global__ __launch_bounds__(64 * kUpperWaves) void k_iir_scan_upper(uint64_t E1
     const double prev = __shfl_up(mine[i], 1, 64);
     st[i] = r > 0 ? prev : 0.0;
   }
-  mat_vec_acc<P>(m1r, s2, st);
+  mat_vec_acc<double, P>(m1r, s2, st);
   if (live) {
 #pragma unroll
     for (int i = 0; i < P; ++i) starts1[(e1 * P + i) * NC + comp] = st[i];
@@ -810,20 +785,24 @@ static hipError_t run_resident(const Coeffs& cf, S* xh, S* yh, const S* x, S* y,
   ra.ticket = reinterpret_cast<uint32_t*>(ws + off_ticket);
   ra.status = static_cast<uint32_t*>(status);
   ra.max_polls = max_polls;
-  const bool vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15u) == 0;
   const uint32_t nclear = (uint32_t)std::min<uint64_t>(512, ceil_div<uint64_t>(nagg, 8 * res::kResWG));
   res::k_res_setup<S, P><<<1 + nclear, res::kResWG, 0, st>>>(cf, tabs, reinterpret_cast<uint64_t*>(ws), nagg, ra.ticket);
-  if (vec) {
-    res::k_iir_resident<S, P, true><<<(uint32_t)ntiles, res::kResWG, 0, st>>>(cf, x, xh, yh, n, y, ra);
-  } else {
-    res::k_iir_resident<S, P, false><<<(uint32_t)ntiles, res::kResWG, 0, st>>>(cf, x, xh, yh, n, y, ra);
-  }
+  const auto k = aligned16(x) && aligned16(y) ? res::k_iir_resident<S, P, true> : res::k_iir_resident<S, P, false>;
+  k<<<(uint32_t)ntiles, res::kResWG, 0, st>>>(cf, x, xh, yh, n, y, ra);
   e = launch_status();
   const hipError_t f = hipFreeAsync(ws, st);
   return e != hipSuccess ? e : f;
 }
 
 #endif  // GSDR_TUNING_PROBES
+
+// one chunk pass: 16-byte tile loads / stores when the caller's buffers allow them (vec)
+template <class S, int P, int PASS, bool FUSED>
+static void launch_chunks(uint32_t blocks, hipStream_t st, bool vec, const Coeffs& cf, const S* x, const S* xh,
+                          uint64_t n, const PassArgs<S, PASS, FUSED>& pa) {
+  const auto kernel = vec ? k_iir_chunks<S, P, PASS, true, FUSED> : k_iir_chunks<S, P, PASS, false, FUSED>;
+  kernel<<<blocks, TileShape<S>::WG, 0, st>>>(cf, x, xh, n, pa);
+}
 
 template <class S, int P>
 static hipError_t run(const Coeffs& cf, S* xh, S* yh, const S* x, S* y, uint64_t n, hipStream_t st, PathSel ps) {
@@ -838,111 +817,66 @@ static hipError_t run(const Coeffs& cf, S* xh, S* yh, const S* x, S* y, uint64_t
     return hipErrorNotSupported;
   }
   using A = typename Acc<S>::type;
-  const uint64_t C = ceil_div<uint64_t>(n, kChunk);
-  // level sizes: E[0] = C chunks, E[k+1] = ceil(E[k] / G) until one group remains
-  constexpr uint64_t G = kGroup;
-  uint64_t E[kMaxLevels + 1];
-  int levels = 0;
-  E[0] = C;
-  while (E[levels] > G) {
-    if (levels == kMaxLevels) return hipErrorInvalidValue;
-    E[levels + 1] = ceil_div<uint64_t>(E[levels], G);
-    ++levels;
-  }
-  // workspace: per level the elements (tails / aggregates) and their start states, the matrices,
-  // and a copy of the entry state (the history buffers are rewritten at the end)
-  size_t off[kMaxLevels + 1][2];
-  size_t bytes = 0;
-  for (int k = 0; k <= levels; ++k) {
-    off[k][0] = bytes;
-    bytes += E[k] * P * sizeof(A);
-    off[k][1] = bytes;
-    bytes += E[k] * P * sizeof(A);
-  }
   constexpr bool F = P <= kFusedMaxP;
-  // levels >= 2 and level 1's down-sweep in one launch when level 2 fits (k_iir_scan_upper, which reads
-  // the powers of M_1, M_2, M_3 from the tables)
-  const bool upper = F && levels >= 2 && E[2] <= kUpperE2;
-  const size_t off_m = bytes;
-  bytes += (size_t)(levels + 1) * kGroup * P * P * sizeof(double);  // T[level][r] = M_level^r
-  const size_t off_s0 = bytes;
-  bytes += P * sizeof(A);
-  const size_t off_xh = bytes;  // the caller's input history, copied by the tails pass for the final pass
-  bytes += (P * sizeof(S) + 15) / 16 * 16;
-  char* ws = nullptr;
-  hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&ws), bytes, st);
+  Workspace<A> W{};
+  const ScanPlan& pl = W.pl;
+  if (!scan_plan(n, P, sizeof(A), sizeof(S), F, &W.pl)) return hipErrorInvalidValue;
+  hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&W.ws), pl.bytes, st);
   if (e != hipSuccess) return e;
-  auto elems = [&](int k) { return reinterpret_cast<A*>(ws + off[k][0]); };
-  auto starts = [&](int k) { return reinterpret_cast<A*>(ws + off[k][1]); };
-  auto table = [&](int k) { return reinterpret_cast<double*>(ws + off_m) + (size_t)k * kGroup * P * P; };
-  A* s0 = reinterpret_cast<A*>(ws + off_s0);
-  S* xh_copy = reinterpret_cast<S*>(ws + off_xh);
-  const int K = cf.K;
-  const int Pk = K - 1;  // live state components (<= P); the rest stay zero
-
-  constexpr int WG = TileShape<S>::WG;
-  const uint64_t ntiles = ceil_div<uint64_t>(n, TileShape<S>::TS);
-  if (ntiles >= 0x7fffffffull) return hipErrorInvalidValue;  // one workgroup per tile (k_iir_chunks)
-  const uint32_t blocks = (uint32_t)ntiles;
-  const SetupArgs sa{yh, s0, table(0), levels, xh, xh_copy};
-  const bool vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15u) == 0;
-  // fused: the tails pass leaves level-0 inclusive prefixes in starts(0) and the group aggregates in
-  // elems(1); the final pass finishes level 0 itself
-  const ScanArgs up_args{reinterpret_cast<double*>(starts(0)), levels > 0 ? reinterpret_cast<double*>(elems(1)) : nullptr,
-                         nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-  if (vec) {
-    k_iir_chunks<S, P, kTails, true, F><<<blocks + 1, WG, 0, st>>>(cf, x, xh, n, nullptr, elems(0), nullptr, sa, up_args);
-  } else {
-    k_iir_chunks<S, P, kTails, false, F><<<blocks + 1, WG, 0, st>>>(cf, x, xh, n, nullptr, elems(0), nullptr, sa,
-                                                                    up_args);
-  }
-  // levels with more than kRestGroups groups: one launch each; the rest: one single-workgroup launch
-  Levels<A> L{};
-  for (int k = 0; k <= levels; ++k) {
-    L.elems[k] = elems(k);
-    L.starts[k] = starts(k);
-    L.T[k] = table(k);
-    L.E[k] = E[k];
-  }
-  L.levels = levels;
-  const int lowest = F ? 1 : 0;  // levels scanned outside the chunk passes
-  int rest = lowest;             // first level handled by the single-workgroup kernels
-  while (rest <= levels && ceil_div<uint64_t>(E[rest], kGroup) > (uint64_t)kRestGroups) ++rest;
-  const int stop = upper ? 2 : rest;  // with k_iir_scan_upper: level 1's up-sweep, then that kernel
-  for (int k = lowest; k < stop; ++k) {
-    k_iir_up<A, P><<<(uint32_t)ceil_div<uint64_t>(E[k], kGroup), 64, 0, st>>>(elems(k), E[k], table(k), starts(k),
-                                                                             elems(k + 1));
-  }
+  auto groups = [&](int k) { return (uint32_t)ceil_div<uint64_t>(pl.E[k], kGroup); };
+  A* s0 = reinterpret_cast<A*>(W.ws + pl.s0);
+  S* xh_copy = reinterpret_cast<S*>(W.ws + pl.xh_copy);
+  const uint32_t blocks = (uint32_t)pl.ntiles;  // one workgroup per tile (k_iir_chunks)
+  const bool vec = aligned16(x) && aligned16(y);
+  // tails pass (plus the setup workgroup); fused, it leaves level 0's inclusive prefixes and group aggregates
+  PassArgs<S, kTails, F> ta{};
+  ta.setup.yh = yh;
+  ta.setup.s0 = s0;
+  ta.setup.T = W.table(0);
+  ta.setup.levels = pl.levels;
+  ta.setup.xh = xh;
+  ta.setup.xh_copy = xh_copy;
   if constexpr (F) {
-    if (upper) {
-      const dim3 grid((uint32_t)ceil_div<uint64_t>(E[2], kUpperWaves), TileShape<S>::NC);
+    ta.incl = W.starts(0);
+    ta.aggs = pl.levels > 0 ? W.elems(1) : nullptr;
+  } else {
+    ta.tails = W.elems(0);
+  }
+  launch_chunks<S, P, kTails, F>(blocks + 1, st, vec, cf, x, xh, n, ta);
+  // up-sweeps of the large levels, then k_iir_scan_upper, or k_iir_scan_rest and the large levels' down-sweeps
+  for (int k = pl.lowest; k < (pl.upper ? 2 : pl.rest); ++k)
+    k_iir_up<A, P><<<groups(k), 64, 0, st>>>(W.elems(k), pl.E[k], W.table(k), W.starts(k), W.elems(k + 1));
+  if constexpr (F) {
+    if (pl.upper) {
+      const dim3 grid((uint32_t)ceil_div<uint64_t>(pl.E[2], kUpperWaves), TileShape<S>::NC);
       k_iir_scan_upper<P><<<grid, 64 * kUpperWaves, 0, st>>>(
-          E[1], E[2], TileShape<S>::NC, table(1), table(2), levels >= 3 ? table(3) : nullptr,
-          reinterpret_cast<const double*>(elems(2)), reinterpret_cast<const double*>(s0),
-          reinterpret_cast<double*>(starts(1)));
+          pl.E[1], pl.E[2], TileShape<S>::NC, W.table(1), W.table(2), pl.levels >= 3 ? W.table(3) : nullptr,
+          reinterpret_cast<const double*>(W.elems(2)), reinterpret_cast<const double*>(s0),
+          reinterpret_cast<double*>(W.starts(1)));
     }
   }
-  if (!upper && rest <= levels) k_iir_scan_rest<A, P><<<1, 64 * kRestWaves, 0, st>>>(L, s0, rest);
-  for (int k = upper ? 0 : stop - 1; k >= lowest; --k) {
-    k_iir_down<A, P><<<(uint32_t)ceil_div<uint64_t>(E[k], kGroup), 64, 0, st>>>(E[k], table(k), starts(k + 1),
-                                                                               starts(k));
+  if (!pl.upper) {
+    if (pl.rest <= pl.levels) k_iir_scan_rest<A, P><<<1, 64 * kRestWaves, 0, st>>>(W, s0, pl.rest);
+    for (int k = pl.rest - 1; k >= pl.lowest; --k)
+      k_iir_down<A, P><<<groups(k), 64, 0, st>>>(pl.E[k], W.table(k), W.starts(k + 1), W.starts(k));
   }
-  // the last chunk writes the caller's history itself (round 4: one launch fewer than a separate history
-  // kernel); the input history it reads comes from the tails pass's copy
-  const ScanArgs down_args{reinterpret_cast<double*>(starts(0)), nullptr, table(0),
-                           levels > 0 ? reinterpret_cast<const double*>(starts(1)) : nullptr,
-                           reinterpret_cast<const double*>(s0), reinterpret_cast<float*>(xh),
-                           reinterpret_cast<float*>(yh), Pk};
-  const S* xh_in = xh ? xh_copy : nullptr;
-  if (vec) {
-    k_iir_chunks<S, P, kFinal, true, F><<<blocks, WG, 0, st>>>(cf, x, xh_in, n, starts(0), nullptr, y, SetupArgs{},
-                                                               down_args);
+  // final pass; fused, it finishes level 0 itself. Its last chunk writes the caller's history (no launch for that)
+  PassArgs<S, kFinal, F> fa{};
+  fa.y = y;
+  if constexpr (F) {
+    fa.incl = W.starts(0);
+    fa.T0 = W.table(0);
+    fa.gstart = pl.levels > 0 ? W.starts(1) : nullptr;
+    fa.s0 = s0;
   } else {
-    k_iir_chunks<S, P, kFinal, false, F><<<blocks, WG, 0, st>>>(cf, x, xh_in, n, starts(0), nullptr, y, SetupArgs{},
-                                                                down_args);
+    fa.starts = W.starts(0);
   }
+  fa.xh_out = reinterpret_cast<float*>(xh);
+  fa.yh_out = reinterpret_cast<float*>(yh);
+  fa.Pk = cf.K - 1;  // live state components (<= P); the rest stay zero
+  launch_chunks<S, P, kFinal, F>(blocks, st, vec, cf, x, xh ? xh_copy : nullptr, n, fa);
   e = launch_status();
-  const hipError_t f = hipFreeAsync(ws, st);
+  const hipError_t f = hipFreeAsync(W.ws, st);
   return e != hipSuccess ? e : f;
 }
 
@@ -1004,7 +938,7 @@ GSDR_C_LINKAGE hipError_t gsdrIirCCCustom(const float* bCoeffs, const float* aCo
 }
 
 #ifdef GSDR_TUNING_PROBES
-// Tuning-probe build only (libgsdr_probes.so; tools/ and tests/test_gpu_iir_single_pass.py bind them by name):
+// Tuning-probe build only (libgsdr_probes.so; tools/ and tests/test_gpu_iir.py bind them by name):
 // gsdrIirFF / gsdrIirCC on the single-pass kernel, chosen per call. maxPolls bounds every wait in polling rounds
 // (2^22 is the measured setting; 0 makes every tile that has to wait give up at once, which is how the status
 // path is tested); hipErrorNotSupported for K > 9 or more than 2^16 tiles. A give-up is reported by

@@ -217,6 +217,33 @@ def test_iir_scan_paths(cuda, iir_fn, order, n):
     assert e <= IIR_TOL
 
 
+@pytest.mark.parametrize("order,n", [(16, 4101), (31, 4101), (16, 131105), (31, 131105), (4, 131105)])
+def test_iir_complex_scan_routes_with_history(cuda, order, n):
+    """Complex samples with complex histories through the scan routes the real-valued tests leave out. Orders 16
+    and 31 run the unfused chunk passes: 4101 samples are 129 chunks, so level 0 itself goes through
+    k_iir_scan_rest (last group and last chunk partial); 131105 samples are 4098 chunks (E1 = 65, E2 = 2), level 0
+    by k_iir_up / k_iir_down and levels 1, 2 in k_iir_scan_rest, a partial group at every level. Order 4 at
+    131105 samples is the fused route with levels == 2: k_iir_scan_upper on both components from a non-zero
+    entry state. The multi-pass scan only (ops.iir): the single-pass kernel refuses K > 9."""
+    from gsdr_amd import ops
+
+    b, a = design("poles", order)
+    rng = np.random.default_rng(1000 * order + n)
+
+    def cplx(m):
+        return (rng.uniform(-1, 1, m) + 1j * rng.uniform(-1, 1, m)).astype(np.complex64)
+
+    x, xh, yh = cplx(n), cplx(order), cplx(order)
+    xh_d, yh_d = dev(xh, cuda), dev(yh, cuda)
+    y = ops.iir(dev(b, cuda), dev(a, cuda), dev(x, cuda), xh_d, yh_d).cpu().numpy()
+    want, xh2, yh2 = o.iir(b, a, x, xh, yh)
+    e = err(y, want)
+    print(f"poles{order} n={n} complex err={e:.2e}")
+    assert e <= IIR_TOL
+    assert np.array_equal(xh_d.cpu().numpy(), xh2)  # last K-1 inputs, exactly
+    assert np.array_equal(yh_d.cpu().numpy(), y[::-1][:order])  # last K-1 outputs as written
+
+
 @pytest.mark.parametrize("order", [1, 2])
 @pytest.mark.parametrize("n", [3 * 8192 + 1, 3 * (1 << 21) + 5])
 @pytest.mark.parametrize("cplx", [False, True])

@@ -101,6 +101,11 @@ def main():
                                                   yis[k % 4].data_ptr(), n5, 0, st),
         "gsdrIirCC": lambda lib, k: lib.gsdrIirCC(bb.data_ptr(), aa.data_ptr(), 5, None, None, xics[k % 4].data_ptr(),
                                                   yics[k % 4].data_ptr(), n5, 0, st),
+        # the launch-bound end: 2^16 samples of the same buffers
+        "gsdrIirFF_64k": lambda lib, k: lib.gsdrIirFF(bb.data_ptr(), aa.data_ptr(), 5, None, None, xis[k % 4].data_ptr(),
+                                                      yis[k % 4].data_ptr(), 1 << 16, 0, st),
+        "gsdrIirCC_64k": lambda lib, k: lib.gsdrIirCC(bb.data_ptr(), aa.data_ptr(), 5, None, None, xics[k % 4].data_ptr(),
+                                                      yics[k % 4].data_ptr(), 1 << 16, 0, st),
         "gsdrIirFF9": lambda lib, k: lib.gsdrIirFF(bb8.data_ptr(), aa8.data_ptr(), 9, None, None, xis[k % 4].data_ptr(),
                                                    yis[k % 4].data_ptr(), n5, 0, st),
         "gsdrIirCC9": lambda lib, k: lib.gsdrIirCC(bb8.data_ptr(), aa8.data_ptr(), 9, None, None, xics[k % 4].data_ptr(),
