@@ -177,7 +177,7 @@ def xlating_fir(x, taps, rf_sample_rate, tuning_frequency, channel_frequency, de
 
 
 def _multi(name, x, taps, fs, tune, chans, devs, decimation, first_sample_index, num_outputs, fm,
-           odt=torch.float32):
+           odt=torch.float32, out=None):
     import ctypes
 
     if x.dtype not in (torch.complex64, torch.int8):
@@ -191,7 +191,11 @@ def _multi(name, x, taps, fs, tune, chans, devs, decimation, first_sample_index,
     if num_outputs > 0:
         _require_samples(x, x.dtype, "input", need)
     C = len(chans)
-    out = torch.empty((C, num_outputs), dtype=odt, device=x.device)
+    if out is None:
+        out = torch.empty((C, num_outputs), dtype=odt, device=x.device)
+    _require(out, odt, "output", C * num_outputs)
+    if out.shape != (C, num_outputs):  # channel c's row starts at c * numOutputs elements
+        raise ValueError(f"output must be a ({C}, {num_outputs}) tensor, got {tuple(out.shape)}")
     fa = (ctypes.c_float * max(C, 1))(*chans)
     args = [fs, tune, fa]
     if fm:
@@ -203,24 +207,24 @@ def _multi(name, x, taps, fs, tune, chans, devs, decimation, first_sample_index,
 
 
 def fm_demod_multi(x, taps, rf_sample_rate, tuning_frequency, channel_frequencies, frequency_deviations,
-                   decimation, first_sample_index=0, num_outputs=None):
+                   decimation, first_sample_index=0, num_outputs=None, out=None):
     """gsdrxFmDemodMulti: out[c] = gsdrFmDemod with channel_frequencies[c], frequency_deviations[c]."""
     return _multi("gsdrxFmDemodMulti", x, taps, rf_sample_rate, tuning_frequency, channel_frequencies,
-                  frequency_deviations, decimation, first_sample_index, num_outputs, True)
+                  frequency_deviations, decimation, first_sample_index, num_outputs, True, out=out)
 
 
 def am_demod_multi(x, taps, rf_sample_rate, tuning_frequency, channel_frequencies, decimation,
-                   first_sample_index=0, num_outputs=None):
+                   first_sample_index=0, num_outputs=None, out=None):
     """gsdrxAmDemodMulti: out[c] = gsdrAmDemod with channel_frequencies[c]."""
     return _multi("gsdrxAmDemodMulti", x, taps, rf_sample_rate, tuning_frequency, channel_frequencies, None,
-                  decimation, first_sample_index, num_outputs, False)
+                  decimation, first_sample_index, num_outputs, False, out=out)
 
 
 def xlating_fir_multi(x, taps, rf_sample_rate, tuning_frequency, channel_frequencies, decimation,
-                      first_sample_index=0, num_outputs=None):
+                      first_sample_index=0, num_outputs=None, out=None):
     """gsdrxXlatingFirMulti: out[c] = gsdrxXlatingFir with channel_frequencies[c] (complex64 rows)."""
     return _multi("gsdrxXlatingFirMulti", x, taps, rf_sample_rate, tuning_frequency, channel_frequencies, None,
-                  decimation, first_sample_index, num_outputs, False, torch.complex64)
+                  decimation, first_sample_index, num_outputs, False, torch.complex64, out=out)
 
 
 def quad_fm_demod(x, gain, num_outputs=None, out=None):

@@ -20,6 +20,8 @@
  * its true start state), so float32 results differ from a sequential float32 loop by rounding only;
  * tests bound the difference against a float64 evaluation. Scratch memory comes from the stream-
  * ordered allocator on `cudaStream` (hipMallocAsync / hipFreeAsync); the call stays asynchronous.
+ * `input` and `output` must not overlap: the final pass re-reads the samples before each tile while
+ * other tiles write their outputs.
  * gsdrIir*Custom accept samplesPerThread in [1, 32] as the reference does; the results do not depend
  * on it (the chunking is chosen internally).
  */

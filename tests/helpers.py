@@ -8,6 +8,49 @@ import numpy as np
 FLOAT_TOL = 1e-5
 
 
+# Guarded output buffers: a kernel's output is a view in the middle of a sentinel-filled buffer, so a store outside
+# [output, output + n) lands in the test's own memory and is seen (an exactly sized torch allocation hides a spill of a
+# few elements in the allocator's block rounding).
+GUARD = 64
+
+
+def default_sentinel(dtype):
+    """A finite value no kernel here produces (every output is O(1), or an angle below a few hundred)."""
+    return complex(-7.5, 1234.5) if dtype.is_complex else -4321.5
+
+
+def guarded(cuda, dtype, n, off=0, sentinel=None):
+    """(buf, view): buf holds GUARD + n + GUARD + 4 elements of `sentinel`, view = buf[GUARD + off:][:n]. buf is 16-byte
+    aligned, so `off` (0 .. 3 elements) alone decides the alignment of the view."""
+    import torch
+
+    assert 0 <= off <= 4
+    sentinel = default_sentinel(dtype) if sentinel is None else sentinel
+    buf = torch.full((GUARD + n + GUARD + 4,), sentinel, dtype=dtype, device=cuda)
+    assert buf.data_ptr() % 16 == 0
+    return buf, buf[GUARD + off:GUARD + off + n]
+
+
+def check_guards(buf, view, sentinel=None, what=""):
+    """Every element of buf outside view still holds the sentinel, compared bytewise (a NaN or a -0.0 written over a
+    guard is seen too). view: any contiguous view of buf (a (C, N) view of C * N elements included); `what` names the
+    case in the failure message."""
+    import torch
+
+    sentinel = default_sentinel(buf.dtype) if sentinel is None else sentinel
+    size = buf.element_size()
+    lo = view.storage_offset() - buf.storage_offset()
+    hi = lo + view.numel()
+    assert view.is_contiguous() and 0 <= lo <= hi <= buf.numel()
+    torch.cuda.synchronize()
+    raw = buf.cpu().numpy()
+    want = np.full(1, sentinel, dtype=raw.dtype).view(np.uint8)
+    for name, part, at in (("before", raw[:lo], 0), ("after", raw[hi:], hi)):
+        bad = np.flatnonzero(np.any(part.view(np.uint8).reshape(-1, size) != want, axis=1))
+        assert bad.size == 0, (f"{what}: wrote outside [output, output + {view.numel()}): {bad.size} guard elements {name} it, "
+                               f"buffer indices {(bad[:8] + at).tolist()} (output at {lo}), values {part[bad[:4]]}")
+
+
 def bound(taps, x, D, N, k0=0, k1=None):
     """S_k = sum_i |t_i| |x_{kD+i}| in float64, for k in [k0, k1)."""
     k1 = N if k1 is None else k1

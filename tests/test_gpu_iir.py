@@ -15,6 +15,7 @@ import pytest
 import torch
 from scipy import signal
 
+from helpers import check_guards, guarded
 from oracle import oracle as o
 
 pytestmark = pytest.mark.gpu
@@ -297,3 +298,193 @@ def test_iir_single_pass_give_up_is_reported(cuda):
     assert rc == 0 and lib.gsdrxIirSinglePassStatus(cuda.index, st) == 0
     assert err(y.cpu().numpy(), want) <= IIR_TOL
     assert not np.array_equal(xh.cpu().numpy(), xh0)
+
+
+# The edges of the contract in include/gsdr/iir.h, on the multi-pass scan (ops.iir): output and history writes stay
+# inside their buffers at every alignment, calls shorter than the history, one history buffer alone, a[0] unused.
+# Orders: every compiled state size P (1, 2, 4, 8, 16, 31), at it and just above the one below (K - 1 < P, where the
+# history write has to stop short of the compiled state; orders 16, 17, 31 run the unfused chunk passes).
+EDGE_ORDERS = [1, 2, 3, 4, 5, 8, 9, 16, 17, 31]
+
+
+def samples(rng, m, cplx):
+    v = rng.uniform(-1, 1, m).astype(np.float32)
+    return (v + 1j * rng.uniform(-1, 1, m)).astype(np.complex64) if cplx else v
+
+
+def shifted(t, off):
+    """The same samples `off` elements off 16-byte alignment (run_fir's construction, test_gpu_fir.py)."""
+    if off == 0:
+        return t
+    y = torch.cat([torch.zeros(off, dtype=t.dtype, device=t.device), t])[off:]
+    assert t.data_ptr() % 16 == 0 and y.data_ptr() % 16 == (off * t.element_size()) % 16
+    return y
+
+
+def guarded_history(cuda, h, off=1):
+    """A history buffer of K - 1 samples in the middle of a sentinel buffer: (buf, view), view holding h."""
+    buf, view = guarded(cuda, torch.complex64 if np.iscomplexobj(h) else torch.float32, h.size, off)
+    view.copy_(torch.from_numpy(h))
+    return buf, view
+
+
+def history_after(new, before):
+    """The K - 1 newest samples, newest first, of `before` (newest first) followed by `new` (oldest first)."""
+    return np.concatenate([new[::-1], before])[:before.size]
+
+
+@pytest.mark.parametrize("cplx", [False, True])
+@pytest.mark.parametrize("order", EDGE_ORDERS)
+def test_iir_output_bounds_and_alignment(cuda, order, cplx):
+    """k_iir_chunks picks whole-tile float4 loads / stores from aligned16(x) && aligned16(y) and writes the ragged last
+    tile per sample: one sample to two tiles of 4,096 complex / 8,192 real samples (one below / above each tile
+    edge, one chunk of 32 +- 1), and levels = 2 on both routes (131,105 samples, orders 4 and 31), with the input
+    and the output each on and off 16-byte alignment. The output is a view inside a sentinel buffer, and so are both
+    histories: nothing outside them changes, the outputs meet the float64 oracle, and they are the same bits at
+    every alignment."""
+    from gsdr_amd import ops
+
+    b, a = design("poles", order)
+    bd, ad = dev(b, cuda), dev(a, cuda)
+    rng = np.random.default_rng(100 * order + cplx)
+    dt = torch.complex64 if cplx else torch.float32
+    sizes = [1, 2, 5, 31, 33, 2047, 2049, 4095, 4097, 8195] + ([131105] if order in (4, 31) else [])
+    offs = [(0, 0), (1, 0), (0, 1), (1, 1)] + ([] if cplx else [(3, 3)])
+    for n in sizes:
+        x, xh, yh = samples(rng, n, cplx), samples(rng, order, cplx), samples(rng, order, cplx)
+        want, xh2, _ = o.iir(b, a, x, xh, yh)
+        xd = dev(x, cuda)
+        first = None
+        for xo, yo in offs:
+            case = f"order {order} complex={cplx} n={n} offsets x {xo} y {yo}"
+            hx_buf, hx = guarded_history(cuda, xh)
+            hy_buf, hy = guarded_history(cuda, yh)
+            buf, view = guarded(cuda, dt, n, yo)
+            got = ops.iir(bd, ad, shifted(xd, xo), hx, hy, out=view)
+            assert got.data_ptr() == view.data_ptr() and got.shape == view.shape, case
+            check_guards(buf, view, what=case + ", output")
+            check_guards(hx_buf, hx, what=case + ", inputHistory")
+            check_guards(hy_buf, hy, what=case + ", outputHistory")
+            y = view.cpu().numpy()
+            if first is None:
+                first = y
+                e = err(y, want)
+                assert e <= IIR_TOL, f"{case}: error {e:.2e}"
+            else:
+                assert y.tobytes() == first.tobytes(), f"{case}: outputs differ from the aligned call's"
+            assert hx.cpu().numpy().tobytes() == xh2.tobytes(), case
+            assert np.array_equal(hy.cpu().numpy(), history_after(y, yh)), case
+
+
+@pytest.mark.parametrize("cplx", [False, True])
+@pytest.mark.parametrize("order", EDGE_ORDERS)
+def test_iir_history_write_stops_at_k_minus_1(cuda, order, cplx):
+    """The final pass's last chunk holds the compiled state (P entries) and writes K - 1 of them to the caller's
+    history buffers (the i < Pk guard of k_iir_chunks): with both buffers K - 1 samples in the middle of sentinel
+    buffers, at every alignment of the buffer, the sentinels on both sides survive calls shorter than, as long as and
+    longer than the history."""
+    from gsdr_amd import ops
+
+    b, a = design("poles", order)
+    bd, ad = dev(b, cuda), dev(a, cuda)
+    rng = np.random.default_rng(200 * order + cplx)
+    for n in (1, order, 33, 2049):
+        for off in (0, 1) if cplx else (0, 1, 2, 3):
+            case = f"order {order} complex={cplx} n={n} history offset {off}"
+            x, xh, yh = samples(rng, n, cplx), samples(rng, order, cplx), samples(rng, order, cplx)
+            hx_buf, hx = guarded_history(cuda, xh, off)
+            hy_buf, hy = guarded_history(cuda, yh, off)
+            y = ops.iir(bd, ad, dev(x, cuda), hx, hy).cpu().numpy()
+            check_guards(hx_buf, hx, what=case + ", inputHistory")
+            check_guards(hy_buf, hy, what=case + ", outputHistory")
+            assert hx.cpu().numpy().tobytes() == history_after(x, xh).tobytes(), case
+            assert hy.cpu().numpy().tobytes() == history_after(y, yh).tobytes(), case
+
+
+@pytest.mark.parametrize("cplx", [False, True])
+@pytest.mark.parametrize("order", EDGE_ORDERS)
+def test_iir_short_calls_with_history(cuda, order, cplx):
+    """numElements below, at and above K - 1 (iir.h: the histories then keep older entries): the input history is the
+    K - 1 newest of (old history, x) exactly, the output history the K - 1 newest of (old history, y as written)
+    exactly -- old entries travel float -> double -> float unrounded -- and a second call continues from them as the
+    float64 oracle does from the same handed-over values. (K - 2 = 0 at order 1: a call with no samples succeeds and
+    leaves the histories alone.)"""
+    from gsdr_amd import ops
+
+    K = order + 1
+    b, a = design("poles", order)
+    bd, ad = dev(b, cuda), dev(a, cuda)
+    rng = np.random.default_rng(300 * order + cplx)
+    for n in sorted({1, 2, K - 2, K - 1, K}):
+        case = f"order {order} complex={cplx} n={n}"
+        x, xh, yh = samples(rng, n, cplx), samples(rng, order, cplx), samples(rng, order, cplx)
+        hx_buf, hx = guarded_history(cuda, xh)
+        hy_buf, hy = guarded_history(cuda, yh)
+        y = ops.iir(bd, ad, dev(x, cuda), hx, hy).cpu().numpy()
+        check_guards(hx_buf, hx, what=case + ", inputHistory")
+        check_guards(hy_buf, hy, what=case + ", outputHistory")
+        xh1, yh1 = hx.cpu().numpy(), hy.cpu().numpy()
+        assert xh1.tobytes() == history_after(x, xh).tobytes(), case
+        assert yh1.tobytes() == history_after(y, yh).tobytes(), case
+        if n:
+            want, _, _ = o.iir(b, a, x, xh, yh)
+            assert err(y, want) <= IIR_TOL, case
+        x2 = samples(rng, 50, cplx)
+        y2 = ops.iir(bd, ad, dev(x2, cuda), hx, hy).cpu().numpy()
+        want2, xh2, _ = o.iir(b, a, x2, xh1, yh1)
+        assert err(y2, want2) <= IIR_TOL, case + ", second call"
+        assert hx.cpu().numpy().tobytes() == xh2.tobytes(), case + ", second call"
+        assert hy.cpu().numpy().tobytes() == history_after(y2, yh1).tobytes(), case + ", second call"
+
+
+@pytest.mark.parametrize("which", ["input", "output"])
+@pytest.mark.parametrize("cplx", [False, True])
+@pytest.mark.parametrize("order", [4, 16])
+def test_iir_one_history_buffer(cuda, order, cplx, which):
+    """Only inputHistory, or only outputHistory (the other null: zero state, not written): the outputs are the
+    oracle's for the same pattern, and the buffer that was given is updated as when both are."""
+    from gsdr_amd import ops
+
+    b, a = design("poles", order)
+    bd, ad = dev(b, cuda), dev(a, cuda)
+    rng = np.random.default_rng(400 * order + cplx)
+    for n in (3, 5000):
+        case = f"order {order} complex={cplx} n={n} {which} history only"
+        x, h = samples(rng, n, cplx), samples(rng, order, cplx)
+        h_buf, hd = guarded_history(cuda, h)
+        if which == "input":
+            want, _, _ = o.iir(b, a, x, h, None)
+            y = ops.iir(bd, ad, dev(x, cuda), hd, None).cpu().numpy()
+        else:
+            want, _, _ = o.iir(b, a, x, None, h)
+            y = ops.iir(bd, ad, dev(x, cuda), None, hd).cpu().numpy()
+        check_guards(h_buf, hd, what=case)
+        e = err(y, want)
+        assert e <= IIR_TOL, f"{case}: error {e:.2e}"
+        assert hd.cpu().numpy().tobytes() == history_after(x if which == "input" else y, h).tobytes(), case
+
+
+@pytest.mark.parametrize("a0", [7.5, 0.0, float("nan")])
+@pytest.mark.parametrize("order", [2, 8, 31])
+def test_iir_a0_is_not_used(cuda, order, a0):
+    """iir.h: a[0] is taken as 1 whatever it holds. The outputs and both histories are the same bits as with
+    a[0] = 1, for real and complex samples."""
+    from gsdr_amd import ops
+
+    b, a = design("poles", order)
+    assert a[0] == 1.0
+    a_other = a.copy()
+    a_other[0] = a0
+    n = 5000
+    for cplx in (False, True):
+        rng = np.random.default_rng(500 * order + cplx)
+        x, xh, yh = samples(rng, n, cplx), samples(rng, order, cplx), samples(rng, order, cplx)
+        got = []
+        for coeffs in (a, a_other):
+            hx, hy = dev(xh.copy(), cuda), dev(yh.copy(), cuda)
+            y = ops.iir(dev(b, cuda), dev(coeffs, cuda), dev(x, cuda), hx, hy)
+            got.append((y.cpu().numpy(), hx.cpu().numpy(), hy.cpu().numpy()))
+        want, _, _ = o.iir(b, a, x, xh, yh)
+        assert err(got[0][0], want) <= IIR_TOL
+        for one, other in zip(*got):
+            assert np.all(np.isfinite(one.view(np.float32))) and one.tobytes() == other.tobytes(), (order, a0, cplx)

@@ -10,14 +10,13 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import FLOAT_TOL, bound, normwise_err
+from helpers import FLOAT_TOL, bound, check_guards, guarded, normwise_err
 from oracle import oracle as o
 
 pytestmark = pytest.mark.gpu
 
 FS, TUNE, CHAN = 1.0e6, 0.0, 1.0e5
 N_SMALL = 2 * 4096 + 11  # at least three NCO cells at every tiled decimation
-GUARD = 64
 SENTINEL = complex(-7.5, 1234.5)
 
 
@@ -41,13 +40,11 @@ def guarded_call(cuda, x, taps, D, n0, N):
     """ops.xlating_fir into the middle of a sentinel-filled buffer; returns the outputs after checking the guards."""
     from gsdr_amd import ops
 
-    buf = torch.full((N + 2 * GUARD,), SENTINEL, dtype=torch.complex64, device=cuda)
-    out = buf[GUARD:GUARD + N]
+    buf, out = guarded(cuda, torch.complex64, N, 0, SENTINEL)
     got = ops.xlating_fir(x, taps, FS, TUNE, CHAN, D, n0, N, out=out)
     torch.cuda.synchronize()
     assert got.data_ptr() == out.data_ptr()
-    guards = torch.cat([buf[:GUARD], buf[GUARD + N:]]).cpu().numpy()
-    assert np.all(guards == np.complex64(SENTINEL)), "wrote outside [output, output + numOutputs)"
+    check_guards(buf, out, SENTINEL)
     return out.cpu().numpy()
 
 
