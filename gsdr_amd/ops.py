@@ -17,7 +17,7 @@ __all__ = [
     "qpsk_modulate_templated", "qpsk_demodulate_templated",
     "qpsk256_init", "qpsk256_modulate", "qpsk256_modulate_awgn", "qpsk256_demodulate", "qpsk256_modulate_4x", "qpsk256_demodulate_4x",
     "nco_phase_increment", "stream_of",
-    "fm_demod_multi", "am_demod_multi", "xlating_fir", "xlating_fir_multi", "iir", "add_const", "multiply", "add_to_magnitude", "abs_", "cosine", "int8_to_norm_float",
+    "fm_demod_multi", "am_demod_multi", "xlating_fir", "xlating_fir_multi", "resample", "resample_inputs_for", "iir", "add_const", "multiply", "add_to_magnitude", "abs_", "cosine", "int8_to_norm_float",
 ]
 
 
@@ -173,6 +173,42 @@ def xlating_fir(x, taps, rf_sample_rate, tuning_frequency, channel_frequency, de
     check(name, getattr(lib, name)(rf_sample_rate, tuning_frequency, channel_frequency, decimation,
                                    first_sample_index, _ptr(taps), T, _ptr(x), _ptr(out), num_outputs,
                                    _dev(x), stream_of(x)))
+    return out
+
+
+def resample_inputs_for(interpolation: int, decimation: int, phase: int, num_taps: int, num_outputs: int) -> int:
+    """gsdrxResampleInputsFor: input samples resample() reads for these arguments (0 for no outputs or arguments the
+    call rejects)."""
+    if min(interpolation, decimation, phase, num_taps, num_outputs) < 0:
+        return 0
+    if max(interpolation, decimation, phase) >= 1 << 32 or max(num_taps, num_outputs) >= 1 << 64:
+        return 0
+    return int(lib.gsdrxResampleInputsFor(interpolation, decimation, phase, num_taps, num_outputs))
+
+
+def resample(taps, x, interpolation, decimation, phase=0, num_outputs=None, out=None):
+    """gsdrxResampleFF / FC by x's dtype (gsdr_ext.h): the rate of x times interpolation / decimation through real
+    taps designed at interpolation times the input rate; `phase` in [0, interpolation) is output 0's offset in
+    the zero-stuffed stream. num_outputs defaults to the most outputs x supports."""
+    if x.dtype not in (torch.float32, torch.complex64):
+        raise TypeError(f"input: expected float32 or complex64, got {x.dtype}")
+    _require(x, x.dtype, "input")
+    _require(taps, torch.float32, "taps")
+    L, M, q = int(interpolation), int(decimation), int(phase)
+    if not (1 <= L < 1 << 32 and 1 <= M < 1 << 32 and 0 <= q < L):
+        raise ValueError(f"need interpolation, decimation in [1, 2^32) and phase in [0, interpolation); got {L}, {M}, {q}")
+    T = taps.numel()
+    if num_outputs is None:
+        # inputs_for(n) <= len(x)  <=>  q + (n - 1) M + T <= len(x) L
+        room = x.numel() * L - q - T
+        num_outputs = room // M + 1 if room >= 0 and x.numel() > 0 else 0
+    if num_outputs > 0:
+        _require(x, x.dtype, "input", max(1, resample_inputs_for(L, M, q, T, num_outputs)))
+    if out is None:
+        out = torch.empty(num_outputs, dtype=x.dtype, device=x.device)
+    _require(out, x.dtype, "output", num_outputs)
+    name = "gsdrxResampleFC" if x.dtype == torch.complex64 else "gsdrxResampleFF"
+    check(name, getattr(lib, name)(L, M, q, _ptr(taps), T, _ptr(x), _ptr(out), num_outputs, _dev(x), stream_of(x)))
     return out
 
 

@@ -266,6 +266,68 @@ GSDR_C_LINKAGE GSDR_PUBLIC hipError_t gsdrxXlatingFirMulti(
     int32_t cudaDevice,
     hipStream_t cudaStream) GSDR_NO_EXCEPT;
 
+/**
+ * Polyphase rational resampling FIR: the sample rate times interpolation / decimation (L / M, both >= 1), through
+ * real taps[0 .. numTaps) designed at L times the input rate. Correlation form, no tap reversal, as gsdrFir*. With
+ * q = phase in [0, L), for m in [0, numOutputs):
+ *     s(m)      = q + m * M                    (64-bit: the window's start in the zero-stuffed stream)
+ *     i0(m)     = (L - s(m) mod L) mod L       the first tap that meets a real sample
+ *     n0(m)     = (s(m) + i0(m)) / L           that sample's index in input
+ *     output[m] = sum_{p >= 0, i0 + p L < numTaps} taps[i0 + p L] * input[n0 + p]
+ * which is gsdrFirFF / FC with decimation M over the zero-stuffed signal u[j] = input[j / L] if L divides j, else
+ * 0, output m's window starting at u[q + m M]. Only the listed products are formed (a structural zero never
+ * meets an Inf or NaN sample), each output component as one ascending-p fmaf chain from +0; an output whose
+ * window holds no tap (i0 >= numTaps) is +0.
+ * The call reads gsdrxResampleInputsFor(L, M, phase, numTaps, numOutputs)
+ *     = floor((q + (numOutputs - 1) * M + numTaps - 1) / L) + 1 input samples.
+ * A stream that starts at (input, phase0), cut into calls by hand: the call whose first output has absolute index
+ * m0 takes U = phase0 + m0 * M and is given input + U / L and phase = U mod L. It reproduces the single call bit
+ * for bit, wherever the cuts fall and whatever the alignment of the advanced pointer: the kernel is chosen from
+ * (L, M, numTaps, sample type) alone.
+ * numOutputs == 0 returns hipSuccess with nothing launched, whatever the other arguments are.
+ * hipErrorInvalidValue, before any device call, for interpolation == 0, decimation == 0, phase >= interpolation,
+ * a null input or output, null taps with numTaps > 0, phase + (numOutputs - 1) * decimation + numTaps not
+ * fitting in 63 bits, or more outputs than one launch takes (2^32 - 1 threads of 8 outputs each, or of one
+ * where the taps or a tile's input span exceed the 64 KB of LDS a workgroup uses). numTaps == 0 writes zeros.
+ * interpolation == 1 is gsdrFirFF / gsdrFirFC with the same decimation, bit for bit.
+ */
+GSDR_C_LINKAGE GSDR_PUBLIC hipError_t gsdrxResampleFF(
+    uint32_t interpolation,
+    uint32_t decimation,
+    uint32_t phase,
+    const float* taps,
+    size_t numTaps,
+    const float* input,
+    float* output,
+    size_t numOutputs,
+    int32_t cudaDevice,
+    hipStream_t cudaStream) GSDR_NO_EXCEPT;
+
+/** gsdrxResampleFF on complex samples (real taps): both components through the same chain. */
+GSDR_C_LINKAGE GSDR_PUBLIC hipError_t gsdrxResampleFC(
+    uint32_t interpolation,
+    uint32_t decimation,
+    uint32_t phase,
+    const float* taps,
+    size_t numTaps,
+    const hipFloatComplex* input,
+    hipFloatComplex* output,
+    size_t numOutputs,
+    int32_t cudaDevice,
+    hipStream_t cudaStream) GSDR_NO_EXCEPT;
+
+/**
+ * Input samples gsdrxResampleFF / FC read for these arguments (host only, no device work):
+ * floor((phase + (numOutputs - 1) * decimation + numTaps - 1) / interpolation) + 1, and 0 for numOutputs == 0 or
+ * arguments the calls reject (also 0 for numTaps == 0 with phase == 0 and numOutputs == 1: nothing is spanned).
+ */
+GSDR_C_LINKAGE GSDR_PUBLIC size_t gsdrxResampleInputsFor(
+    uint32_t interpolation,
+    uint32_t decimation,
+    uint32_t phase,
+    size_t numTaps,
+    size_t numOutputs) GSDR_NO_EXCEPT;
+
 /*
  * Config 5's channel model (BASELINE configs[4]: QPSK256 modulate -> AWGN -> demod): the output of
  * gsdrQpsk256Modulate (the table set by gsdrQpsk256InitConstellation for constellationType) plus
