@@ -96,6 +96,7 @@ SIGNATURES = {
     "gsdrxResampleFF": (_err, [_u32, _u32, _u32, _p, _sz, _p, _p, _sz, _i32, _p]),
     "gsdrxResampleFC": (_err, [_u32, _u32, _u32, _p, _sz, _p, _p, _sz, _i32, _p]),
     "gsdrxResampleInputsFor": (_sz, [_u32, _u32, _u32, _sz, _sz]),
+    "gsdrxChannelizer": (_err, [_u32, _u32, _sz, _p, _sz, _int, _p, _p, _sz, _i32, _p]),
     # stream.h
     "gsdrxStreamCreate": (_err, [ctypes.POINTER(_p), _int, _int, _u32, _p, _sz, _f, _f, _f, _f, _sz, _i32]),
     "gsdrxStreamCreateMulti": (_err, [ctypes.POINTER(_p), _int, _int, _u32, _p, _sz, _f, _f, _p, _p, _u32, _sz, _i32]),

@@ -17,7 +17,7 @@ __all__ = [
     "qpsk_modulate_templated", "qpsk_demodulate_templated",
     "qpsk256_init", "qpsk256_modulate", "qpsk256_modulate_awgn", "qpsk256_demodulate", "qpsk256_modulate_4x", "qpsk256_demodulate_4x",
     "nco_phase_increment", "stream_of",
-    "fm_demod_multi", "am_demod_multi", "xlating_fir", "xlating_fir_multi", "resample", "resample_inputs_for", "iir", "add_const", "multiply", "add_to_magnitude", "abs_", "cosine", "int8_to_norm_float",
+    "fm_demod_multi", "am_demod_multi", "xlating_fir", "xlating_fir_multi", "channelizer", "resample", "resample_inputs_for", "iir", "add_const", "multiply", "add_to_magnitude", "abs_", "cosine", "int8_to_norm_float",
 ]
 
 
@@ -261,6 +261,35 @@ def xlating_fir_multi(x, taps, rf_sample_rate, tuning_frequency, channel_frequen
     """gsdrxXlatingFirMulti: out[c] = gsdrxXlatingFir with channel_frequencies[c] (complex64 rows)."""
     return _multi("gsdrxXlatingFirMulti", x, taps, rf_sample_rate, tuning_frequency, channel_frequencies, None,
                   decimation, first_sample_index, num_outputs, False, torch.complex64, out=out)
+
+
+def channelizer(x, taps, num_channels, decimation, first_sample_index=0, num_outputs=None, out=None):
+    """gsdrxChannelizer (gsdr_ext.h): a polyphase filter bank, num_channels (2, 4, ..., 64) uniformly spaced channels
+    of x through the real prototype `taps`, each decimated by `decimation`; out[c, m] is channel c (centred c / M of
+    the sample rate above the tuned frequency) at output time m. complex64 or int8 I/Q input. num_outputs defaults
+    to the most output times x supports."""
+    if x.dtype not in (torch.complex64, torch.int8):
+        raise TypeError(f"input: expected complex64 or int8 I/Q, got {x.dtype}")
+    _require(x, x.dtype, "input")
+    _require(taps, torch.float32, "taps")
+    M, D, n0 = int(num_channels), int(decimation), int(first_sample_index)
+    if M not in (2, 4, 8, 16, 32, 64):
+        raise ValueError(f"num_channels must be 2, 4, 8, 16, 32 or 64; got {M}")
+    if not (1 <= D < 1 << 32 and 0 <= n0 < 1 << 64):
+        raise ValueError(f"need decimation in [1, 2^32) and first_sample_index in [0, 2^64); got {D}, {n0}")
+    T, L = taps.numel(), _nsamp(x)
+    if num_outputs is None:
+        num_outputs = (L - T) // D + 1 if L >= T else 0
+    if num_outputs > 0:
+        _require_samples(x, x.dtype, "input", (num_outputs - 1) * D + T)
+    if out is None:
+        out = torch.empty((M, num_outputs), dtype=torch.complex64, device=x.device)
+    _require(out, torch.complex64, "output", M * num_outputs)
+    if out.shape != (M, num_outputs):  # channel c's row starts at c * numOutputs elements
+        raise ValueError(f"output must be a ({M}, {num_outputs}) tensor, got {tuple(out.shape)}")
+    check("gsdrxChannelizer", lib.gsdrxChannelizer(M, D, n0, _ptr(taps), T, 1 if x.dtype == torch.int8 else 0, _ptr(x),
+                                                   _ptr(out), num_outputs, _dev(x), stream_of(x)))
+    return out
 
 
 def quad_fm_demod(x, gain, num_outputs=None, out=None):

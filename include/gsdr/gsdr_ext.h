@@ -328,6 +328,49 @@ GSDR_C_LINKAGE GSDR_PUBLIC size_t gsdrxResampleInputsFor(
     size_t numTaps,
     size_t numOutputs) GSDR_NO_EXCEPT;
 
+/**
+ * Polyphase filter bank (channelizer): numChannels = M uniformly spaced channels of one input in one pass, each
+ * filtered by the real prototype taps[0 .. numTaps) and decimated by D = decimation. With
+ * n(m, i) = firstSampleIndex + m * D + i, for c in [0, M) and m in [0, numOutputs):
+ *     output[c * numOutputs + m] = sum_{i < numTaps} taps[i] * input[m * D + i] * exp(-j 2 pi ((c * n(m, i)) mod M) / M)
+ * Channel c is the band centred c * fs / M above the tuned frequency (channels c > M / 2 are the negative
+ * frequencies). The NCO increment c * 2^32 / M is exact, so row c is mathematically
+ * gsdrxXlatingFir(rfSampleRate = M, tuningFrequency = 0, channelFrequency = c, D, firstSampleIndex, taps, ...);
+ * the two agree to parity, not to bits. The layout is channel-major, as gsdrxXlatingFirMulti's. The call reads
+ * (numOutputs - 1) * D + numTaps input samples, as gsdrAmDemod does.
+ * Computed as a filter bank: the branch sums v[p] = sum_k taps[p + k M] * input[m D + p + k M], p in [0, M), each
+ * component one ascending-k fmaf chain from +0; an M-point forward DFT over p; and a rotation by
+ * exp(-j 2 pi c r0 / M), r0 = (firstSampleIndex + m D) mod M (64-bit), skipped when r0 == 0. The DFT and rotation
+ * twiddles are correctly rounded. The prototype filter costs numTaps multiply-adds an output time for all
+ * channels together.
+ * M is 2, 4, 8, 16, 32 or 64; larger banks and banks that are not a power of two are not provided. D is any value
+ * >= 1: D == M (critically sampled) and D == M / 2 (2x oversampled) run the tiled kernel, every other D a slower
+ * one output time a thread.
+ * sampleFormat: GSDRX_SAMPLES_CF32, or GSDRX_SAMPLES_CS8 (converted as gsdrInt8ToNormFloat while the tile is
+ * staged: bit-identical to converting first and calling with GSDRX_SAMPLES_CF32).
+ * The kernel is chosen from (M, D, numTaps) alone and the bits of output (c, m) depend only on the taps, on m's
+ * window and on r0(m): a stream cut into calls by hand (the call whose first output is a given input + a * D and
+ * firstSampleIndex + a * D) reproduces one call bit for bit, at any cut and any pointer alignment.
+ * A non-finite sample stays in its windows: an output time whose window holds an Inf or NaN is non-finite in every
+ * channel, every other output is unaffected.
+ * numOutputs == 0 returns hipSuccess with nothing launched, whatever the other arguments are. numTaps == 0 writes
+ * zeros. hipErrorInvalidValue, before any device call, for an M outside the list, decimation == 0, a null input or
+ * output, null taps with numTaps > 0, an unknown sampleFormat, (numOutputs - 1) * D + numTaps or M * numOutputs
+ * not fitting in 63 bits, or more output times than one launch takes (2^32 - 1 threads, one output time each).
+ */
+GSDR_C_LINKAGE GSDR_PUBLIC hipError_t gsdrxChannelizer(
+    uint32_t numChannels,
+    uint32_t decimation,
+    size_t firstSampleIndex,
+    const float* taps,
+    size_t numTaps,
+    int sampleFormat,
+    const void* input,
+    hipFloatComplex* output,
+    size_t numOutputs,
+    int32_t cudaDevice,
+    hipStream_t cudaStream) GSDR_NO_EXCEPT;
+
 /*
  * Config 5's channel model (BASELINE configs[4]: QPSK256 modulate -> AWGN -> demod): the output of
  * gsdrQpsk256Modulate (the table set by gsdrQpsk256InitConstellation for constellationType) plus
