@@ -18,6 +18,12 @@
  *   gsdrAbs:            out = |x|
  * Each writes exactly numElements outputs (the reference's `x > n` bound check also wrote
  * out[numElements]). numElements == 0 returns hipSuccess without a launch.
+ *
+ * In place: where the output has the input's type, `output` may be exactly `input` (gsdrAddConstFF / CC,
+ * gsdrAddToMagnitude, gsdrAbs) and `out` exactly `in1` or exactly `in2` (gsdrMultiplyFF / CC; gsdrMultiplyCF:
+ * `out` exactly `in1`): every element is read before it is written, by the thread that writes it, and the result
+ * equals the out-of-place one bit for bit (tests/test_gpu_arith.py). Any other overlap of an output with an
+ * input (a shifted or partial one) is not supported.
  */
 #ifndef GSDR_ARITHMETIC_H_
 #define GSDR_ARITHMETIC_H_

@@ -405,7 +405,9 @@ GSDR_C_LINKAGE GSDR_PUBLIC hipError_t gsdrxQpsk256ModulateAwgn(
  * followed by gsdrQpsk256Demodulate(noisySymbols, outputBytes, numSymbols, constellationType, ...) write --
  * the same noisy symbols and the same decisions, bit for bit -- but for the rectangular table
  * (constellationType 0) one kernel demodulates each noisy symbol from the registers it was formed in, so the
- * noisy buffer is written once and never read back. Other tables run the two calls. Same errors as
+ * noisy buffer is written once and never read back. Other tables run the two calls. outputBytes may be exactly
+ * inputBytes (decoding in place, as the two calls allow): each lane uses only the symbol bytes it later overwrites
+ * itself and has loaded them by then (tests/test_gpu_qpsk.py); any other overlap is not supported. Same errors as
  * gsdrxQpsk256ModulateAwgn, plus hipErrorInvalidValue for a null outputBytes.
  */
 GSDR_C_LINKAGE GSDR_PUBLIC hipError_t gsdrxQpsk256ModulateAwgnDemodulate(

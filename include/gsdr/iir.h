@@ -19,7 +19,9 @@
  * dimensional state carried across chunks with transition-matrix powers, then each chunk re-run from
  * its true start state), so float32 results differ from a sequential float32 loop by rounding only;
  * tests bound the difference against a float64 evaluation. Scratch memory comes from the stream-
- * ordered allocator on `cudaStream` (hipMallocAsync / hipFreeAsync); the call stays asynchronous.
+ * ordered allocator on `cudaStream` (hipMallocAsync / hipFreeAsync) and every launch is ordered on that stream.
+ * A first call returns at once; a further call on a stream that is still busy returns only when the stream has
+ * drained, because the runtime's hipFreeAsync then waits on the host (tests/test_gpu_stream_order.py).
  * `input` and `output` must not overlap: the final pass re-reads the samples before each tile while
  * other tiles write their outputs.
  * gsdrIir*Custom accept samplesPerThread in [1, 32] as the reference does; the results do not depend

@@ -51,6 +51,164 @@ def check_guards(buf, view, sentinel=None, what=""):
                                f"buffer indices {(bad[:8] + at).tolist()} (output at {lo}), values {part[bad[:4]]}")
 
 
+# Gated streams (test_gpu_stream_order.py): the library's work is enqueued on a non-blocking side stream behind a
+# sleeping kernel (the gate) and behind the copies that bring the true inputs in, while the device is otherwise
+# idle. Whatever the library issues on another stream (a kernel, a memset, a history copy) or assumes finished on
+# the host then runs before the copy-in, on the decoy inputs, and its result differs from the synchronised
+# reference. The outputs are refilled with the sentinel behind the gate as well, so a write that ran early is lost
+# even where it does not depend on the inputs (a memset). The gate ends by itself: nothing ever waits for the host.
+def raw_bytes(t):
+    """t's storage bytes as a flat uint8 tensor (a bitwise comparison: NaNs and signed zeros count)."""
+    import torch
+
+    t = torch.view_as_real(t) if t.is_complex() else t
+    return t.contiguous().view(-1).view(torch.uint8)
+
+
+def stream_sentinel(dtype):
+    import torch
+
+    return 0xA5 if dtype == torch.uint8 else default_sentinel(dtype)
+
+
+class GatedJob:
+    """One side stream's work for run_gated_jobs().
+
+    inputs:  (live, true, decoy) device tensors of one shape: `live` is what the entry point reads.
+    outputs: pre-allocated device tensors the entry point writes (the same addresses in both runs).
+    inouts:  (live, true, decoy) like inputs, for buffers a call also writes (IIR histories): snapshotted too.
+    steps:   callables step(phase), phase "reference" or "gated", each enqueueing library calls on torch's current
+             stream; host-side state (a Stream object) is the step's own business, one object a phase.
+    on_default_stream: the control: the gated run issues the steps on the idle default stream instead of the side
+             stream (the copy-in stays gated), which a working harness must see as a mismatch."""
+
+    def __init__(self, inputs, outputs, steps, inouts=(), on_default_stream=False):
+        self.inputs, self.outputs, self.inouts = list(inputs), list(outputs), list(inouts)
+        self.steps = list(steps)
+        self.on_default_stream = on_default_stream
+        for live, true, decoy in self.inputs + self.inouts:
+            assert live.shape == true.shape == decoy.shape and live.dtype == true.dtype == decoy.dtype
+        self.watched = self.outputs + [live for live, _, _ in self.inouts]
+
+
+_SIDE_STREAMS = []   # streams that passed side_streams()'s check before: tried first, and checked again
+
+
+def side_streams(cuda, count, gate_cycles):
+    """`count` of torch's non-blocking streams that the device runs independently of the default stream and of each
+    other, checked now: with a short sleep (a tenth of the gate) queued on the one, a one-element kernel on the other
+    finishes while the first still sleeps. The runtime places its streams on a few hardware queues, and two streams on
+    one queue run in order whatever the program says: behind such a side stream a kernel that the library wrongly
+    issued on the default stream would wait for the gate like everything else, and the fault would go unseen."""
+    import torch
+
+    probe = torch.zeros(1, device=cuda)
+    nap = max(1, gate_cycles // 10)
+
+    def independent(sleeper, other):
+        torch.cuda.synchronize(cuda)
+        asleep, ran = torch.cuda.Event(), torch.cuda.Event()
+        with torch.cuda.stream(sleeper):
+            torch.cuda._sleep(nap)
+            asleep.record(sleeper)
+        with torch.cuda.stream(other):
+            probe.zero_()
+            ran.record(other)
+        ran.synchronize()
+        return not asleep.query()
+
+    default = torch.cuda.default_stream(cuda)
+    chosen = []
+    candidates = list(_SIDE_STREAMS)
+    for _ in range(64):
+        if len(chosen) == count:
+            break
+        s = candidates.pop(0) if candidates else torch.cuda.Stream(device=cuda)
+        if any(s.cuda_stream == c.cuda_stream for c in chosen):
+            continue
+        if all(independent(s, o) and independent(o, s) for o in [default] + chosen):
+            chosen.append(s)
+    torch.cuda.synchronize(cuda)
+    assert len(chosen) == count, f"found {len(chosen)} of {count} streams that run independently of the default stream"
+    for s in chosen:
+        if not any(s.cuda_stream == c.cuda_stream for c in _SIDE_STREAMS):
+            _SIDE_STREAMS.append(s)
+    return chosen
+
+
+def run_gated_jobs(cuda, gate_cycles, jobs):
+    """Reference (synchronised, default stream), arm (decoys in, sentinels out), then every job behind its own gate on
+    its own non-blocking side stream (side_streams()), the jobs' steps enqueued alternately. Asserts that every gate was still closed when
+    the host had finished enqueueing (else the run is inconclusive and fails). Returns, per job, a list of
+    (reference clone, gated snapshot) pairs, one per output and in/out buffer."""
+    import contextlib
+
+    import torch
+
+    def fill(job, decoy):
+        for live, true, dec in job.inputs + job.inouts:
+            live.copy_(dec if decoy else true)
+        for out in job.outputs:
+            out.fill_(stream_sentinel(out.dtype))
+
+    # 1. reference: device idle, default stream, one job after the other
+    refs = []
+    for job in jobs:
+        torch.cuda.synchronize(cuda)
+        fill(job, decoy=False)
+        torch.cuda.synchronize(cuda)
+        for step in job.steps:
+            step("reference")
+        torch.cuda.synchronize(cuda)
+        refs.append([t.clone() for t in job.watched])
+    # 2. arm; the snapshots are allocated here (an allocation behind the gate could wait for the device)
+    snaps = []
+    for job in jobs:
+        fill(job, decoy=True)
+        snaps.append([torch.full_like(t, stream_sentinel(t.dtype)) for t in job.watched])
+    sides = side_streams(cuda, len(jobs), gate_cycles)
+    dones = [torch.cuda.Event() for _ in jobs]
+    torch.cuda.synchronize(cuda)
+    # 3. gated run
+    for job, side in zip(jobs, sides):
+        with torch.cuda.stream(side):
+            torch.cuda._sleep(gate_cycles)
+            for live, true, _ in job.inputs + job.inouts:
+                live.copy_(true, non_blocking=True)
+            for out in job.outputs:   # whatever was written before this point (a memset on another stream) is lost
+                out.fill_(stream_sentinel(out.dtype))
+    for k in range(max(len(job.steps) for job in jobs)):
+        for job, side in zip(jobs, sides):
+            if k < len(job.steps):
+                with contextlib.nullcontext() if job.on_default_stream else torch.cuda.stream(side):
+                    job.steps[k]("gated")
+    for job, side, snap, done in zip(jobs, sides, snaps, dones):
+        with torch.cuda.stream(side):
+            for s, t in zip(snap, job.watched):
+                s.copy_(t, non_blocking=True)
+            done.record(side)
+    # 4. the gates were closed while all of that was enqueued
+    closed = [not done.query() for done in dones]
+    # 5. compare
+    for side in sides:
+        side.synchronize()
+    torch.cuda.synchronize(cuda)
+    assert all(closed), f"inconclusive: a gate of {gate_cycles} cycles ended before the host had enqueued the work"
+    return [list(zip(r, s)) for r, s in zip(refs, snaps)]
+
+
+def run_gated(cuda, gate_cycles, inputs, outputs, steps, inouts=(), on_default_stream=False):
+    """run_gated_jobs() for one stream: the list of (reference, snapshot) pairs."""
+    return run_gated_jobs(cuda, gate_cycles, [GatedJob(inputs, outputs, steps, inouts, on_default_stream)])[0]
+
+
+def mismatches(pairs):
+    """Indices of the (reference, snapshot) pairs that differ in any bit."""
+    import torch
+
+    return [k for k, (r, s) in enumerate(pairs) if not torch.equal(raw_bytes(r), raw_bytes(s))]
+
+
 def bound(taps, x, D, N, k0=0, k1=None):
     """S_k = sum_i |t_i| |x_{kD+i}| in float64, for k in [k0, k1)."""
     k1 = N if k1 is None else k1

@@ -119,6 +119,53 @@ def test_unaligned_pointers(cuda):
     assert same_bits(host(outf), o.add_const(y[1:], 1.25))
 
 
+# In-place calls (arithmetic.h: `output` may be exactly `input`, `out` exactly `in1` or `in2`). name -> (dtype of a,
+# dtype of b or None, which operand the output is, call(ops, a, b, out)).
+IN_PLACE = {
+    "add_const_ff": ("f", None, "a", lambda ops, a, b, out: ops.add_const(a, 3.14, out=out)),
+    "add_const_cc": ("c", None, "a", lambda ops, a, b, out: ops.add_const(a, 1.5 - 2.5j, out=out)),
+    "multiply_ff_in1": ("f", "f", "a", lambda ops, a, b, out: ops.multiply(a, b, out=out)),
+    "multiply_ff_in2": ("f", "f", "b", lambda ops, a, b, out: ops.multiply(a, b, out=out)),
+    "multiply_cc_in1": ("c", "c", "a", lambda ops, a, b, out: ops.multiply(a, b, out=out)),
+    "multiply_cc_in2": ("c", "c", "b", lambda ops, a, b, out: ops.multiply(a, b, out=out)),
+    "abs": ("f", None, "a", lambda ops, a, b, out: ops.abs_(a, out=out)),
+    "add_to_magnitude": ("c", None, "a", lambda ops, a, b, out: ops.add_to_magnitude(a, 2.5, out=out)),
+}
+
+
+@pytest.mark.parametrize("off", [0, 1], ids=["aligned", "one-element-off"])
+@pytest.mark.parametrize("n", [1, 1023, 10_007])
+@pytest.mark.parametrize("name", list(IN_PLACE))
+def test_in_place_equals_out_of_place(cuda, name, n, off):
+    """The output is one of the inputs, exactly: the same bits as into a separate buffer of the same alignment, and
+    the other operand untouched. 10,007 elements: four full blocks on the 16-byte path (aligned views) plus a
+    ragged one element by element; a view one element past a 16-byte boundary runs element by element throughout."""
+    from gsdr_amd import ops
+
+    ka, kb, which, call = IN_PLACE[name]
+
+    def view(kind, seed):
+        host_values = rand_c(n, seed) if kind == "c" else rand_f(n, seed)
+        base = torch.zeros(n + 4, dtype=torch.from_numpy(host_values[:1]).dtype, device=cuda)
+        assert base.data_ptr() % 16 == 0
+        v = base[off:off + n]
+        v.copy_(dev(host_values, cuda))
+        assert v.data_ptr() % 16 == (off * v.element_size()) % 16
+        return v
+
+    a = view(ka, n + 1)
+    b = view(kb, n + 2) if kb else None
+    fresh = view(ka, n + 3)
+    want = host(call(ops, a, b, fresh)).copy()
+    a0, b0 = host(a).copy(), (host(b).copy() if kb else None)
+    out = a if which == "a" else b
+    got = call(ops, a, b, out)
+    assert got.data_ptr() == out.data_ptr()
+    assert same_bits(host(got), want), (name, n, off)
+    if kb:   # the operand that is not the output still holds its values
+        assert same_bits(host(b if which == "a" else a), b0 if which == "a" else a0)
+
+
 def test_exactly_n_written_and_zero_length(cuda):
     from gsdr_amd import abi, ops
 

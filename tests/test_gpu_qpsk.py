@@ -488,3 +488,27 @@ def test_qpsk256_fused_config5_bit_exact(cuda):
     assert np.array_equal(dec.cpu().numpy(), o.qpsk256_demod(table, rx_np, nthreads=_threads()))
     ser = float((dec != syms).float().mean())
     assert 1e-4 < ser < 1e-2
+
+
+@pytest.mark.parametrize("n", [1, 5, 6, 7, 383, 384, 385, 4607, 4608, 4609])  # 6 a lane step, 384 a wave step, 4608 a workgroup
+@pytest.mark.parametrize("first", [0, 1, 2**33 + 3])  # first % 3: 0, 1, 2
+def test_qpsk256_fused_round_trip_decodes_in_place(cuda, n, first):
+    """outputBytes is inputBytes, exactly (gsdr_ext.h; valid with the two calls, whose second reads only the noisy
+    symbols): the fused kernel loads a lane's symbols one step ahead of its decision stores, and its last lanes load
+    from an address moved back into bytes that other lanes own and drop them. Noisy symbols and decisions equal
+    the two-call result computed from a copy of the input, bit for bit."""
+    from gsdr_amd import ops
+
+    sigma, seed = 0.05, 0x5EED0005
+    ops.qpsk256_init(0, 1.0)
+    syms = dev(np.random.default_rng(n + first % 1000).integers(0, 256, n, dtype=np.uint8), cuda)
+    rx2 = ops.qpsk256_modulate_awgn(syms.clone(), 0, sigma, seed, first)
+    dec2 = ops.qpsk256_demodulate(rx2, 0)
+    buf = syms.clone()
+    rx1, dec1 = ops.qpsk256_modulate_awgn_demodulate(buf, 0, sigma, seed, first, out=buf)
+    assert dec1.data_ptr() == buf.data_ptr()
+    torch.cuda.synchronize()
+    assert rx1.cpu().numpy().tobytes() == rx2.cpu().numpy().tobytes()
+    assert torch.equal(dec1, dec2)
+    if n >= 4607:
+        assert not torch.equal(dec1, syms)   # sigma = 0.05 flips some decisions: the buffer was rewritten
