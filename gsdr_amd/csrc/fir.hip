@@ -58,15 +58,15 @@ hipError_t launch_stream_probe(const FirJob& j, hipStream_t s, bool nt) {
 hipError_t launch_fc_probe(const FirJob& j, hipStream_t s) {
   switch (j.variant) {
     case 104:  // compute only (no staging; the tile holds whatever LDS held)
-      return launch_poly<float, float2, 4, 4, 16, 256, kModeFir, 2, true>(j, s);
+      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, 2, true>(j, s);
     case 105:  // staging only, plain loads
-      return launch_poly<float, float2, 4, 4, 16, 256, kModeFir, 1>(j, s);
+      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, 1>(j, s);
     case 107:  // staging only, non-temporal loads
-      return launch_poly<float, float2, 4, 4, 16, 256, kModeFir, 1, true>(j, s);
+      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, 1, true>(j, s);
     case 113:  // matrix-core kernel with register taps, compute only
-      return launch_mfma_bc<256, 9, 2>(j, s);
+      return launch_mfma_bc_shape<2>(j, s);
     case 117:  // staging only by LDS-DMA, non-temporal
-      return launch_poly<float, float2, 4, 4, 16, 256, kModeFir, 1, true, false, 0, true>(j, s);
+      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, 1, true, false, 0, true>(j, s);
     // FM chain (config 3 shape) split: 120 full FM kernel, 121 no NCO mix, 122 no discriminator (plain
     // float store), 123 neither, 124 staging + NCO + discriminator without the FIR, 125 staging only
     case 120:
@@ -81,12 +81,12 @@ hipError_t launch_fc_probe(const FirJob& j, hipStream_t s) {
       c.nco_inc = 429496730u;  // 0.1 fs
       c.fm_gain = 7.957747f;   // fs / (2 pi 0.02 fs)
       switch (j.variant) {
-        case 120: return launch_poly<float, float2, 4, 4, 16, 256, kModeFm, 0, true>(c, s);
-        case 121: return launch_poly<float, float2, 4, 4, 16, 256, kModeFm, 8, true>(c, s);
-        case 122: return launch_poly<float, float2, 4, 4, 16, 256, kModeFm, 16, true>(c, s);
-        case 123: return launch_poly<float, float2, 4, 4, 16, 256, kModeFm, 24, true>(c, s);
-        case 124: return launch_poly<float, float2, 4, 4, 16, 256, kModeFm, 1, true>(c, s);
-        default: return launch_poly<float, float2, 4, 4, 16, 256, kModeFm, 25, true>(c, s);
+        case 120: return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFm, 0, true>(c, s);
+        case 121: return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFm, 8, true>(c, s);
+        case 122: return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFm, 16, true>(c, s);
+        case 123: return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFm, 24, true>(c, s);
+        case 124: return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFm, 1, true>(c, s);
+        default: return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFm, 25, true>(c, s);
       }
     }
     // FM chain (config 3 shape) tile-shape sweep: 130 default (R 4, JC 16, WG 256), 131 R 8 WG 128,
@@ -104,22 +104,22 @@ hipError_t launch_fc_probe(const FirJob& j, hipStream_t s) {
       c.nco_inc = 429496730u;  // 0.1 fs
       c.fm_gain = 7.957747f;   // fs / (2 pi 0.02 fs)
       switch (j.variant) {
-        case 130: return launch_poly<float, float2, 4, 4, 16, 256, kModeFm, 0, true>(c, s);
-        case 131: return launch_poly<float, float2, 4, 8, 16, 128, kModeFm, 0, true>(c, s);
-        case 132: return launch_poly<float, float2, 4, 4, 8, 256, kModeFm, 0, true>(c, s);
-        case 133: return launch_poly<float, float2, 4, 2, 16, 256, kModeFm, 0, true>(c, s);
-        case 134: return launch_poly<float, float2, 4, 4, 16, 128, kModeFm, 0, true>(c, s);
-        case 135: return launch_poly<float, float2, 4, 8, 8, 128, kModeFm, 0, true>(c, s);
-        default: return launch_poly<float, float2, 4, 4, 16, 256, kModeFm, 0, true, true>(c, s);
+        case 130: return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFm, 0, true>(c, s);
+        case 131: return launch_poly_shape<float, float2, 4, 8, 16, 128, kModeFm, 0, true>(c, s);
+        case 132: return launch_poly_shape<float, float2, 4, 4, 8, 256, kModeFm, 0, true>(c, s);
+        case 133: return launch_poly_shape<float, float2, 4, 2, 16, 256, kModeFm, 0, true>(c, s);
+        case 134: return launch_poly_shape<float, float2, 4, 4, 16, 128, kModeFm, 0, true>(c, s);
+        case 135: return launch_poly_shape<float, float2, 4, 8, 8, 128, kModeFm, 0, true>(c, s);
+        default: return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFm, 0, true, true>(c, s);
       }
     }
     // LDS-read probe: the default kernel with the register window served from the
     // thread's own R rows only (4 of 19 ds_read_b128 per column and chunk; wrong results, same FMAs):
     // 140 full kernel, 141 compute only
     case 140:
-      return launch_poly<float, float2, 4, 4, 16, 256, kModeFir, 64, true>(j, s);
+      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, 64, true>(j, s);
     case 141:
-      return launch_poly<float, float2, 4, 4, 16, 256, kModeFir, 66, true>(j, s);
+      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, 66, true>(j, s);
     case 110:
     case 111:
       return launch_stream_probe(j, s, j.variant == 111);

@@ -34,6 +34,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "fir_plan.hpp"
 #include "stream_step.hpp"
 
 namespace gsdr {
@@ -48,24 +49,19 @@ struct Iq8 {
   int8_t x, y;
 };
 
-// kPerGranule: samples per 16-byte LDS granule. kSrcAlign: bytes one staging load moves from HBM
-// per granule (the alignment the vector path needs).
+// The sample kind of a type (fir_plan.hpp: samples per 16-byte LDS granule, bytes one staging load moves per granule).
 template <class T>
-struct SampleT;
+struct SampleKind;
 template <>
-struct SampleT<float> {
-  static constexpr int kPerGranule = 4;
-  static constexpr int kSrcAlign = 16;
-};
+struct SampleKind<float> : std::integral_constant<int, firplan::kSampleReal> {};
 template <>
-struct SampleT<float2> {
-  static constexpr int kPerGranule = 2;
-  static constexpr int kSrcAlign = 16;
-};
+struct SampleKind<float2> : std::integral_constant<int, firplan::kSampleComplex> {};
 template <>
-struct SampleT<Iq8> {
-  static constexpr int kPerGranule = 2;
-  static constexpr int kSrcAlign = 4;
+struct SampleKind<Iq8> : std::integral_constant<int, firplan::kSampleIq8> {};
+template <class T>
+struct SampleT {
+  static constexpr int kPerGranule = firplan::per_granule(SampleKind<T>::value);
+  static constexpr int kSrcAlign = firplan::src_align(SampleKind<T>::value);
 };
 
 // sample type as held in LDS (what the compute core reads)
@@ -265,12 +261,12 @@ template <class InT, int D, int R, int WG>
 struct TileGeo {
   static constexpr int G = SampleT<InT>::kPerGranule;
   static_assert((R * D) % G == 0, "a thread segment must be whole granules");
-  static constexpr int SG = R * D / G;             // granules per thread segment
-  static constexpr int PAD = (SG % 2 == 0) ? 1 : 0;  // odd lane stride -> conflict-free ds_read_b128
+  static constexpr int SG = firplan::tile_sg(G, D, R);  // granules per thread segment
+  static constexpr int PAD = firplan::tile_pad(SG);     // odd lane stride -> conflict-free ds_read_b128
   static constexpr int SGP = SG + PAD;
-  static constexpr int KT = WG * R;                  // outputs per tile
-  static constexpr int ROUT = R;                     // outputs per segment
-  __host__ __device__ static constexpr uint32_t padded(uint32_t g) { return g + PAD * (g / SG); }
+  static constexpr int KT = WG * R;                     // outputs per tile
+  static constexpr int ROUT = R;                        // outputs per segment
+  __host__ __device__ static constexpr uint32_t padded(uint32_t g) { return firplan::tile_padded(g, SG); }
 };
 
 // Non-temporal (streaming) 16-byte load: global_load_dwordx4 ... nt.
@@ -1596,14 +1592,6 @@ __global__ __launch_bounds__(WG) void k_fir_rt(FirParams p) {
   tile_epilogue<MODE, OutT, 1, WG>(p, out0, accs, ex);
 }
 
-template <class InT>
-constexpr size_t rt_lds_bytes(uint32_t D, uint32_t span_samples, int wg, int mode) {
-  const uint32_t G = SampleT<InT>::kPerGranule;
-  size_t bytes = (size_t)(((uint32_t)(wg - 1) * D + span_samples + G - 1) / G) * 16u;
-  if (mode != kModeFir) bytes += ((size_t)wg * sizeof(float2) + 15) / 16 * 16;
-  return bytes;
-}
-
 // ------------------------------------------------------------------------------------------------
 // Kernel 3: generic fallback (any D, any T, any alignment): one output per thread straight from
 // global memory (L1/L2 absorb the overlap). Used only where the tiled kernels do not apply.
@@ -1719,26 +1707,6 @@ __global__ __launch_bounds__(WG) void k_fir_mfma_bc(FirParams p) {
     if (!all_finite(acc)) ascending_fixup<float, float2, Geo, true, R>(lds, p, D, tid * R, acc);
   }
   tile_epilogue<kModeFir, float2, R, WG, NT>(p, out0, acc, nullptr);
-}
-
-template <int WG>
-constexpr size_t mfma_bc_lds_bytes(uint32_t T) {
-  using Geo = TileGeo<float2, 4, 4, WG>;
-  const uint32_t nseg = (12u + T + 15u) / 16u;
-  const uint32_t NG = (4u * (Geo::KT - 4) + 16u * nseg) / 2;
-  return (size_t)(Geo::padded(NG - 1) + 1) * 16u;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Host-side sizing helpers
-// ------------------------------------------------------------------------------------------------
-template <class InT, int D, int R, int WG>
-constexpr size_t poly_lds_bytes(uint32_t span_samples, int mode) {
-  using Geo = TileGeo<InT, D, R, WG>;
-  const uint32_t NG = ((Geo::KT - 1) * D + span_samples + Geo::G - 1) / Geo::G;
-  size_t bytes = (size_t)(Geo::padded(NG - 1) + 1) * 16u;
-  if (mode != kModeFir) bytes += ((size_t)WG * sizeof(float2) + 15) / 16 * 16;
-  return bytes;
 }
 
 }  // namespace gsdr

@@ -33,6 +33,7 @@
 #pragma once
 
 #include "fir_engine.hpp"
+#include "fir_plan.hpp"
 
 namespace gsdr {
 
@@ -190,10 +191,7 @@ struct I8OutScale {
 #ifndef GSDR_I8_CHAIN_PADP
 #define GSDR_I8_CHAIN_PADP 16
 #endif
-template <uint32_t P>
-__host__ __device__ constexpr uint32_t i8_addr(uint32_t idx) {
-  return idx * 2u + (idx / P) * 16u;
-}
+// (i8_addr<P>: fir_plan.hpp)
 
 // Staging of samples [S0, S0 + SPAN) (absolute offsets into `in`, zero outside [0, L)) as bf16 I and Q
 // planes, in two halves so the next tile's loads can be in flight while this tile is computed (the
@@ -343,18 +341,19 @@ __device__ __forceinline__ void i8_store_planes(const I8Stage<G, SPAN, WG>& st, 
 
 template <int D, int NS_, int NCT_ = 4>
 struct I8Mfma {
-  static constexpr int WG = 256;
-  static constexpr int NCT = NCT_;                  // C tiles (128 outputs) per wave and tile
-  static constexpr int KT = (WG / 64) * NCT * 128;  // outputs per tile (a multiple of 16)
-  static constexpr int MAXNS = NS_;                 // 32-sample K steps: 15 D + T <= 32 NS
-  static constexpr int MAXT = 32 * MAXNS - 15 * D;
-  static constexpr int SPAN = (KT - 16) * D + 32 * MAXNS;  // samples staged per tile
+  // (the sizes: fir_plan.hpp, which the launch plan reads too)
+  static constexpr int WG = firplan::kI8WG;
+  static constexpr int NCT = NCT_;                     // C tiles (128 outputs) per wave and tile
+  static constexpr int KT = firplan::i8_fir_kt(NCT);   // outputs per tile (a multiple of 16)
+  static constexpr int MAXNS = NS_;                    // 32-sample K steps: 15 D + T <= 32 NS
+  static constexpr int MAXT = firplan::i8_fir_maxt(D, MAXNS);
+  static constexpr int SPAN = firplan::i8_fir_span(D, MAXNS, NCT);  // samples staged per tile
   static_assert(SPAN % 8 == 0, "staging moves 8 samples a lane");
   static constexpr uint32_t PADP = GSDR_I8_FIR_PADP;  // pad period (i8_addr)
   __host__ __device__ static constexpr uint32_t addr(uint32_t idx) { return i8_addr<PADP>(idx); }
   // Q plane offset: = 128 (mod 256), so the Q columns' bank groups interleave the I columns'
-  static constexpr uint32_t PLANE = (addr(SPAN) + 255u) / 256u * 256u + 128u;
-  static constexpr uint32_t LDS_BYTES = PLANE + addr(SPAN);
+  static constexpr uint32_t PLANE = firplan::i8_plane<PADP>(SPAN);
+  static constexpr uint32_t LDS_BYTES = firplan::i8_lds_bytes<PADP>(SPAN);
 };
 
 // BPC workgroups per CU (one wave per SIMD each): the register budget is 512 / BPC VGPRs.
@@ -510,19 +509,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BPC, BPC)))
 // ------------------------------------------------------------------------------------------------
 template <int MODE, int NCT_ = 4>
 struct I8ChainMfma {
-  static constexpr int D = 4;
-  static constexpr int WG = 256;
-  static constexpr int NCT = NCT_;                 // C tiles (64 outputs) per wave and tile
-  static constexpr int KT = (WG / 64) * NCT * 64;  // y' per tile (a multiple of 16)
-  static constexpr int STRIDE = MODE == kModeFm ? KT - 16 : KT;
-  static constexpr int MAXNS = 5;
-  static constexpr int MAXT = 32 * MAXNS - 7 * D;  // 132
-  static constexpr int SPAN = (KT - 8) * D + 32 * MAXNS;
+  static constexpr int D = firplan::kI8ChainD;
+  static constexpr int WG = firplan::kI8WG;
+  static constexpr int NCT = NCT_;                        // C tiles (64 outputs) per wave and tile
+  static constexpr int KT = firplan::i8_chain_kt(NCT);    // y' per tile (a multiple of 16)
+  static constexpr int STRIDE = firplan::i8_chain_stride(MODE, NCT);
+  static constexpr int MAXNS = firplan::kI8ChainNs;
+  static constexpr int MAXT = firplan::kI8ChainMaxT;      // 132
+  static constexpr int SPAN = firplan::i8_chain_span(NCT);
   static_assert(SPAN % 4 == 0, "whole granules");
   static constexpr uint32_t PADP = GSDR_I8_CHAIN_PADP;  // pad period (i8_addr)
   __host__ __device__ static constexpr uint32_t addr(uint32_t idx) { return i8_addr<PADP>(idx); }
-  static constexpr uint32_t PLANE = (addr(SPAN) + 255u) / 256u * 256u + 128u;
-  static constexpr uint32_t LDS_BYTES = PLANE + addr(SPAN);
+  static constexpr uint32_t PLANE = firplan::i8_plane<PADP>(SPAN);
+  static constexpr uint32_t LDS_BYTES = firplan::i8_lds_bytes<PADP>(SPAN);
 };
 
 template <int MODE, int LM, int BPC, int NCT>

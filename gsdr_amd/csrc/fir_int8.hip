@@ -46,7 +46,7 @@ hipError_t fir_int8_stream_step(uint64_t outputIndex, size_t decimation, const f
   job.set_step(so);
   DeviceScope scope(device);
   if (scope.status() != hipSuccess) return scope.status();
-  return launch_i8_mfma<4, 3>(job, stream);
+  return launch_i8_mfma(job, stream);
 }
 
 // The same on the tiled kernels (decimations other than 4, or tap counts the matrix-core kernel does not

@@ -8,10 +8,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "fir_plan.hpp"
+
 namespace gsdr {
 
-// kModeIq: the chains' NCO + FIR stage with the complex output stored (gsdrxXlatingFir, xlate.hip)
-enum Mode : int { kModeFir = 0, kModeFm = 1, kModeAm = 2, kModeIq = 3 };
+// (enum Mode { kModeFir, kModeFm, kModeAm, kModeIq }: fir_plan.hpp)
 
 // One streaming step's input (FirParams, fir_engine.hpp): output 0's window starts at sample in_off of the
 // chunk (negative: in the history `hist` of hist_len samples, chunk offset i < 0 being hist[hist_len + i]);
