@@ -9,7 +9,6 @@
 #include <type_traits>
 
 #include "fir_engine.hpp"
-#include "fir_i8_mfma.hpp"
 #include "fir_plan.hpp"
 #include "launch.hpp"
 
@@ -271,70 +270,16 @@ hipError_t launch_d4_variant(const firplan::Plan& pl, const FirParams& p, hipStr
   return hipErrorInvalidValue;
 }
 
-// int8 I/Q FIR on the matrix cores (k_fir_i8_mfma, fir_i8_mfma.hpp): persistent workgroups (their tap fragments
-// are built once), in the shape, staging (G, LM) and output alignment (OA) the plan chose.
-template <int NS, int BPC, int NCT, int PF>
-hipError_t launch_i8_fir_shape(const firplan::Plan& pl, const FirParams& p, hipStream_t s) {
-  auto go = [&](auto g, auto lm) {
-    constexpr int G = decltype(g)::value, LM = decltype(lm)::value;
-    if (pl.OA) {
-      k_fir_i8_mfma<4, NS, G, LM, true, BPC, NCT, PF><<<dim3(pl.grid), dim3(pl.wg), 0, s>>>(p, pl.ns, (uint32_t)pl.tiles);
-    } else {
-      k_fir_i8_mfma<4, NS, G, LM, false, BPC, NCT, PF><<<dim3(pl.grid), dim3(pl.wg), 0, s>>>(p, pl.ns, (uint32_t)pl.tiles);
-    }
-  };
-  using std::integral_constant;
-  if (pl.G == 8 && pl.LM == 1) {
-    go(integral_constant<int, 8>{}, integral_constant<int, 1>{});
-  } else if (pl.LM == 1) {
-    go(integral_constant<int, 4>{}, integral_constant<int, 1>{});
-  } else if (pl.LM == 2) {
-    go(integral_constant<int, 4>{}, integral_constant<int, 2>{});
-  } else {
-    go(integral_constant<int, 8>{}, integral_constant<int, 0>{});
-  }
-  return launch_status();
-}
-
-inline hipError_t launch_i8_fir(const firplan::Plan& pl, const FirParams& p, hipStream_t s) {
-#define GSDR_I8_LAUNCH_SHAPE(NS_, BPC_, NCT_, PF_) \
-  if (pl.NS == NS_ && pl.BPC == BPC_ && pl.NCT == NCT_ && pl.PF == PF_) return launch_i8_fir_shape<NS_, BPC_, NCT_, PF_>(pl, p, s);
-  GSDR_I8_FIR_SHAPES(GSDR_I8_LAUNCH_SHAPE)
-#undef GSDR_I8_LAUNCH_SHAPE
-  return hipErrorInvalidValue;
-}
-
-// int8 I/Q FM / AM chain on the matrix cores (k_chain_i8_mfma): D = 4, T <= 132
-template <int MODE, int NCT>
-hipError_t launch_i8_chain_nct(const firplan::Plan& pl, const FirParams& p, hipStream_t s) {
-  constexpr int BPC = GSDR_CHAIN_BPC;
-  const dim3 grid(pl.grid), block(pl.wg);
-  if (pl.LM == 1) {
-    k_chain_i8_mfma<MODE, 1, BPC, NCT><<<grid, block, 0, s>>>(p, pl.ns, (uint32_t)pl.tiles);
-  } else if (pl.LM == 2) {
-    k_chain_i8_mfma<MODE, 2, BPC, NCT><<<grid, block, 0, s>>>(p, pl.ns, (uint32_t)pl.tiles);
-  } else {
-    k_chain_i8_mfma<MODE, 0, BPC, NCT><<<grid, block, 0, s>>>(p, pl.ns, (uint32_t)pl.tiles);
-  }
-  return launch_status();
-}
-
+// The int8 matrix-core launchers and gsdrxFirFCInt8Variant's (fir_i8_dispatch.hpp). Templates, declared here and
+// defined there, so their kernels are instantiated only in the units whose launch_plan reaches them -- those
+// include that header (fir_int8.hip; fm_am.hip for the chains). A non-template launcher in this header would put its
+// kernels' device code into every unit that includes it, with no host stub to launch them from.
+template <class InT>
+hipError_t launch_i8_fir(const firplan::Plan& pl, const FirParams& p, hipStream_t s);
+template <class InT>
+hipError_t launch_int8_variant(const firplan::Plan& pl, const FirParams& p, hipStream_t s);
 template <int MODE>
-hipError_t launch_i8_chain(const firplan::Plan& pl, const FirParams& p, hipStream_t s) {
-  if (pl.NCT == 1) return launch_i8_chain_nct<MODE, 1>(pl, p, s);  // a short call
-  return launch_i8_chain_nct<MODE, GSDR_CHAIN_NCT>(pl, p, s);
-}
-
-// What gsdrxFirFCInt8Variant's plans launch: the shared tile-shape variants, the generic kernel (7) and the matrix-core
-// sweep (40-46). (Not a template: every translation unit that includes this header has always carried these
-// kernels, whoever calls them.)
-inline hipError_t launch_int8_variant(const firplan::Plan& pl, const FirParams& p, hipStream_t s) {
-  switch (pl.family) {
-    case firplan::kFamI8Fir: return launch_i8_fir(pl, p, s);
-    case firplan::kFamGeneric: return launch_generic_kernel<float, Iq8, kModeFir>(pl, p, s);
-    default: return launch_d4_variant<float, Iq8, kModeFir>(pl, p, s);
-  }
-}
+hipError_t launch_i8_chain(const firplan::Plan& pl, const FirParams& p, hipStream_t s);
 
 // Ablation probes (gsdrxFirFCVariant >= 100; fir.hip, compiled only into the probes library, `make probes`; the
 // product library returns hipErrorInvalidValue for them).
@@ -348,8 +293,8 @@ hipError_t launch_plan(const FirJob& j, const firplan::Plan& pl, hipStream_t s) 
   if (pl.family == firplan::kFamProbe) return launch_fc_probe(j, s);
   const FirParams p = make_params(j, pl);
   if constexpr (kInt8 && MODE == kModeFir) {
-    if (j.D == 4 && j.variant >= 0) return launch_int8_variant(pl, p, s);
-    if (pl.family == firplan::kFamI8Fir) return launch_i8_fir(pl, p, s);
+    if (j.D == 4 && j.variant >= 0) return launch_int8_variant<InT>(pl, p, s);
+    if (pl.family == firplan::kFamI8Fir) return launch_i8_fir<InT>(pl, p, s);
   }
   if constexpr (kInt8 && kRealTaps && (MODE == kModeFm || MODE == kModeAm)) {
     if (pl.family == firplan::kFamI8Chain) return launch_i8_chain<MODE>(pl, p, s);
@@ -380,19 +325,6 @@ hipError_t launch_generic(const FirJob& j, hipStream_t s) {
   firplan::Plan pl;
   const hipError_t e = plan_job<TapT, InT, MODE>(j, firplan::kEntryGeneric, 0, &pl);
   return e != hipSuccess ? e : launch_generic_kernel<TapT, InT, MODE>(pl, make_params(j, pl), s);
-}
-
-// The int8 matrix-core kernels whatever the route (the stream object's one-launch steps at decimation 4).
-inline hipError_t launch_i8_mfma(const FirJob& j, hipStream_t s) {
-  firplan::Plan pl;
-  const hipError_t e = plan_job<float, Iq8, kModeFir>(j, firplan::kEntryI8Fir, 0, &pl);
-  return e != hipSuccess ? e : launch_i8_fir(pl, make_params(j, pl), s);
-}
-template <int MODE>
-hipError_t launch_chain_i8_mfma(const FirJob& j, hipStream_t s) {
-  firplan::Plan pl;
-  const hipError_t e = plan_job<float, Iq8, MODE>(j, firplan::kEntryI8Chain, 0, &pl);
-  return e != hipSuccess ? e : launch_i8_chain<MODE>(pl, make_params(j, pl), s);
 }
 
 // An explicit tile shape (the probes): the plan's tile arithmetic for it, then the kernel. A tap span that does not

@@ -1,7 +1,8 @@
 // gsdr-mi355x: the common body of the gsdrFir* entry points (reference src/fir.cu:73-171): argument
 // checks, the T = 0 case and the kernel dispatch. Each sample-type pair is instantiated in its own
 // translation unit (fir.hip: FC, fir_ff.hip, fir_cc.hip, fir_cf.hip, fir_int8.hip) so they build in
-// parallel.
+// parallel, and each unit's code object holds only the kernels of its own pair: the int8 matrix-core and
+// variant launchers live in fir_i8_dispatch.hpp, which of these five only fir_int8.hip includes.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include "fir_entry.hpp"
+#include "fir_i8_dispatch.hpp"
 #include "gsdr/fir.h"
 #include "gsdr/gsdr_ext.h"
 

@@ -159,13 +159,14 @@ hipError_t channel_step(const gsdrxStream_t& s, const ChainSpec& cs, size_t c, c
     return i8 ? fir_int8_stream_step_tiled(s.D, s.taps, s.T, so, o, n, s.device, st)
               : fir_fc_stream_step(s.D, s.taps, s.T, so, o, n, s.device, st);
   }
-  if (s.kind == GSDRX_STREAM_XLATE) {  // (no matrix-core form: int8 I/Q takes the tiled kernels at every decimation)
-    return xlate_stream_step_tiled(cs, i8, s.chans[c], so, static_cast<hipFloatComplex*>(out), n, s.device, st);
+  // (XLATE has no matrix-core form: int8 I/Q takes the tiled kernels at every decimation)
+  const bool xlate = s.kind == GSDRX_STREAM_XLATE;
+  if (i8 && !xlate) {
+    e = chain_int8_stream_step(cs, s.chans[c], s.devs[c], so, static_cast<float*>(out), n, s.device, st);
   }
-  float* o = static_cast<float*>(out);
-  if (i8) e = chain_int8_stream_step(cs, s.chans[c], s.devs[c], so, o, n, s.device, st);
   if (e != hipErrorNotSupported) return e;
-  return chain_stream_step_tiled(cs, i8, s.chans[c], s.devs[c], so, o, n, s.device, st);
+  ChainStepTiled* step = xlate ? xlate_stream_step_tiled : chain_stream_step_tiled;
+  return step(cs, i8, s.chans[c], s.devs[c], so, out, n, s.device, st);
 }
 
 }  // namespace
@@ -314,13 +315,9 @@ GSDR_C_LINKAGE hipError_t gsdrxStreamProcess(gsdrxStream s, const void* input, s
     const gsdr::ChainSpec cs{mode, s->fs, s->tune, s->D, s->n0 + h0, s->taps, s->T};
     e = hipErrorNotSupported;
     if (C > 1 && s->format != GSDRX_SAMPLES_CS8) {
-      e = s->kind == GSDRX_STREAM_XLATE
-              ? gsdr::xlate_multi_stream_step(cs, s->chans.data(), (uint32_t)C, so,
-                                              reinterpret_cast<hipFloatComplex*>(out), outputCapacity, n_out,
-                                              s->device, cudaStream)
-              : gsdr::chain_multi_stream_step(cs, s->chans.data(), s->devs.data(), (uint32_t)C, so,
-                                              reinterpret_cast<float*>(out), outputCapacity, n_out, s->device,
-                                              cudaStream);
+      gsdr::ChainMultiStep* step =
+          s->kind == GSDRX_STREAM_XLATE ? gsdr::xlate_multi_stream_step : gsdr::chain_multi_stream_step;
+      e = step(cs, s->chans.data(), s->devs.data(), (uint32_t)C, so, out, outputCapacity, n_out, s->device, cudaStream);
     }
     // otherwise one launch per channel; a shape without a one-launch step returns hipErrorNotSupported from
     // channel 0, before anything was launched, and the call takes the seam path below

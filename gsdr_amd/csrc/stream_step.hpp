@@ -60,17 +60,15 @@ hipError_t fir_fc_stream_step(size_t decimation, const float* taps, size_t tapCo
                               hipFloatComplex* output, size_t numOutputs, int32_t device, hipStream_t stream);
 hipError_t fir_int8_stream_step_tiled(size_t decimation, const float* taps, size_t tapCount, const StreamOperands& so,
                                       hipFloatComplex* output, size_t numOutputs, int32_t device, hipStream_t stream);
-hipError_t chain_stream_step_tiled(const ChainSpec& cs, bool int8, float chan, float dev, const StreamOperands& so,
-                                   float* output, size_t numOutputs, int32_t device, hipStream_t stream);
-// the grouped multi-channel kernel on complex float chunks, channel c's outputs at output + c * outStride: fm_am.hip
-hipError_t chain_multi_stream_step(const ChainSpec& cs, const float* chans, const float* devs, uint32_t count,
-                                   const StreamOperands& so, float* output, size_t outStride, size_t numOutputs,
-                                   int32_t device, hipStream_t stream);
-// the frequency-translating FIR (kModeIq) on the tiled kernels, single channel and grouped: xlate.hip
-hipError_t xlate_stream_step_tiled(const ChainSpec& cs, bool int8, float chan, const StreamOperands& so,
-                                   hipFloatComplex* output, size_t numOutputs, int32_t device, hipStream_t stream);
-hipError_t xlate_multi_stream_step(const ChainSpec& cs, const float* chans, uint32_t count, const StreamOperands& so,
-                                   hipFloatComplex* output, size_t outStride, size_t numOutputs, int32_t device,
-                                   hipStream_t stream);
+// The chains' steps (chain_job.hpp) come once per unit that holds chain kernels -- fm_am.hip (cs.mode kModeFm or
+// kModeAm, float outputs) and xlate.hip (kModeIq, complex outputs; dev / devs unused) -- with one parameter list.
+using ChainStepTiled = hipError_t(const ChainSpec& cs, bool int8, float chan, float dev, const StreamOperands& so,
+                                  void* output, size_t numOutputs, int32_t device, hipStream_t stream);
+// the grouped multi-channel kernel on complex float chunks, channel c's outputs at element c * outStride of output
+using ChainMultiStep = hipError_t(const ChainSpec& cs, const float* chans, const float* devs, uint32_t count,
+                                  const StreamOperands& so, void* output, size_t outStride, size_t numOutputs,
+                                  int32_t device, hipStream_t stream);
+ChainStepTiled chain_stream_step_tiled, xlate_stream_step_tiled;
+ChainMultiStep chain_multi_stream_step, xlate_multi_stream_step;
 
 }  // namespace gsdr

@@ -105,75 +105,60 @@ def fir_variant(variant: int, taps: torch.Tensor, x: torch.Tensor, decimation: i
     return out
 
 
-def fm_demod(x, taps, rf_sample_rate, tuning_frequency, channel_frequency, frequency_deviation, decimation,
-             first_sample_index=0, num_outputs=None, out=None):
-    """gsdrFmDemod: NCO shift + low-pass FIR + decimation + FM discriminator (fm.h); int8 I/Q input
-    selects gsdrxFmDemodInt8."""
+def _chain_prepare(x, taps, decimation, num_outputs, out, fm, odt=torch.float32, channels=None):
+    """What every chain wrapper checks before its call: the input and tap dtypes, the default num_outputs (the most
+    x supports), x's length for it, and the output -- a (channels, num_outputs) tensor for the multi forms. An FM
+    output needs one more FIR output than an AM or IQ one."""
     if x.dtype not in (torch.complex64, torch.int8):
         raise TypeError(f"input: expected complex64 or int8 I/Q, got {x.dtype}")
     _require(x, x.dtype, "input")
     _require(taps, torch.float32, "taps")
-    T = taps.numel()
+    T, L = taps.numel(), _nsamp(x)
     if num_outputs is None:
-        num_outputs = max(0, (_nsamp(x) - T) // decimation)
+        num_outputs = max(0, (L - T) // decimation) if fm else ((L - T) // decimation + 1 if L >= T else 0)
     if num_outputs > 0:
-        _require_samples(x, x.dtype, "input", num_outputs * decimation + T)
+        _require_samples(x, x.dtype, "input", (num_outputs if fm else num_outputs - 1) * decimation + T)
+    shape = (num_outputs,) if channels is None else (channels, num_outputs)
     if out is None:
-        out = torch.empty(num_outputs, dtype=torch.float32, device=x.device)
-    _require(out, torch.float32, "output", num_outputs)
-    name = "gsdrxFmDemodInt8" if x.dtype == torch.int8 else "gsdrFmDemod"
-    check(name, getattr(lib, name)(rf_sample_rate, tuning_frequency, channel_frequency, frequency_deviation,
-                                         decimation, first_sample_index, _ptr(taps), T, _ptr(x), _ptr(out),
-                                         num_outputs, _dev(x), stream_of(x)))
+        out = torch.empty(shape, dtype=odt, device=x.device)
+    _require(out, odt, "output", num_outputs * (1 if channels is None else channels))
+    if channels is not None and out.shape != shape:  # channel c's row starts at c * numOutputs elements
+        raise ValueError(f"output must be a {shape} tensor, got {tuple(out.shape)}")
+    return num_outputs, out
+
+
+def _chain(name, x, taps, head, decimation, first_sample_index, num_outputs, out, fm, odt=torch.float32):
+    n, out = _chain_prepare(x, taps, decimation, num_outputs, out, fm, odt)
+    check(name, getattr(lib, name)(*head, decimation, first_sample_index, _ptr(taps), taps.numel(), _ptr(x), _ptr(out),
+                                   n, _dev(x), stream_of(x)))
     return out
+
+
+def fm_demod(x, taps, rf_sample_rate, tuning_frequency, channel_frequency, frequency_deviation, decimation,
+             first_sample_index=0, num_outputs=None, out=None):
+    """gsdrFmDemod: NCO shift + low-pass FIR + decimation + FM discriminator (fm.h); int8 I/Q input
+    selects gsdrxFmDemodInt8."""
+    return _chain("gsdrxFmDemodInt8" if x.dtype == torch.int8 else "gsdrFmDemod", x, taps,
+                  (rf_sample_rate, tuning_frequency, channel_frequency, frequency_deviation), decimation,
+                  first_sample_index, num_outputs, out, True)
 
 
 def am_demod(x, taps, rf_sample_rate, tuning_frequency, channel_frequency, decimation, first_sample_index=0,
              num_outputs=None, out=None):
     """gsdrAmDemod: NCO shift + low-pass FIR + decimation + envelope (am.h); int8 I/Q input selects
     gsdrxAmDemodInt8."""
-    if x.dtype not in (torch.complex64, torch.int8):
-        raise TypeError(f"input: expected complex64 or int8 I/Q, got {x.dtype}")
-    _require(x, x.dtype, "input")
-    _require(taps, torch.float32, "taps")
-    T = taps.numel()
-    L = _nsamp(x)
-    if num_outputs is None:
-        num_outputs = (L - T) // decimation + 1 if L >= T else 0
-    if num_outputs > 0:
-        _require_samples(x, x.dtype, "input", (num_outputs - 1) * decimation + T)
-    if out is None:
-        out = torch.empty(num_outputs, dtype=torch.float32, device=x.device)
-    _require(out, torch.float32, "output", num_outputs)
-    name = "gsdrxAmDemodInt8" if x.dtype == torch.int8 else "gsdrAmDemod"
-    check(name, getattr(lib, name)(rf_sample_rate, tuning_frequency, channel_frequency, decimation,
-                                         first_sample_index, _ptr(taps), T, _ptr(x), _ptr(out), num_outputs,
-                                         _dev(x), stream_of(x)))
-    return out
+    return _chain("gsdrxAmDemodInt8" if x.dtype == torch.int8 else "gsdrAmDemod", x, taps,
+                  (rf_sample_rate, tuning_frequency, channel_frequency), decimation, first_sample_index, num_outputs,
+                  out, False)
 
 
 def xlating_fir(x, taps, rf_sample_rate, tuning_frequency, channel_frequency, decimation, first_sample_index=0,
                 num_outputs=None, out=None):
     """gsdrxXlatingFir: NCO shift + low-pass FIR + decimation, the complex baseband output (gsdr_ext.h); int8 I/Q
     input selects gsdrxXlatingFirInt8."""
-    if x.dtype not in (torch.complex64, torch.int8):
-        raise TypeError(f"input: expected complex64 or int8 I/Q, got {x.dtype}")
-    _require(x, x.dtype, "input")
-    _require(taps, torch.float32, "taps")
-    T = taps.numel()
-    L = _nsamp(x)
-    if num_outputs is None:
-        num_outputs = (L - T) // decimation + 1 if L >= T else 0
-    if num_outputs > 0:
-        _require_samples(x, x.dtype, "input", (num_outputs - 1) * decimation + T)
-    if out is None:
-        out = torch.empty(num_outputs, dtype=torch.complex64, device=x.device)
-    _require(out, torch.complex64, "output", num_outputs)
-    name = "gsdrxXlatingFirInt8" if x.dtype == torch.int8 else "gsdrxXlatingFir"
-    check(name, getattr(lib, name)(rf_sample_rate, tuning_frequency, channel_frequency, decimation,
-                                   first_sample_index, _ptr(taps), T, _ptr(x), _ptr(out), num_outputs,
-                                   _dev(x), stream_of(x)))
-    return out
+    return _chain("gsdrxXlatingFirInt8" if x.dtype == torch.int8 else "gsdrxXlatingFir", x, taps,
+                  (rf_sample_rate, tuning_frequency, channel_frequency), decimation, first_sample_index, num_outputs,
+                  out, False, torch.complex64)
 
 
 def resample_inputs_for(interpolation: int, decimation: int, phase: int, num_taps: int, num_outputs: int) -> int:
@@ -216,28 +201,14 @@ def _multi(name, x, taps, fs, tune, chans, devs, decimation, first_sample_index,
            odt=torch.float32, out=None):
     import ctypes
 
-    if x.dtype not in (torch.complex64, torch.int8):
-        raise TypeError(f"input: expected complex64 or int8 I/Q, got {x.dtype}")
-    _require(x, x.dtype, "input")
-    _require(taps, torch.float32, "taps")
-    T, L = taps.numel(), _nsamp(x)
-    if num_outputs is None:
-        num_outputs = max(0, (L - T) // decimation) if fm else ((L - T) // decimation + 1 if L >= T else 0)
-    need = num_outputs * decimation + T if fm else (num_outputs - 1) * decimation + T
-    if num_outputs > 0:
-        _require_samples(x, x.dtype, "input", need)
     C = len(chans)
-    if out is None:
-        out = torch.empty((C, num_outputs), dtype=odt, device=x.device)
-    _require(out, odt, "output", C * num_outputs)
-    if out.shape != (C, num_outputs):  # channel c's row starts at c * numOutputs elements
-        raise ValueError(f"output must be a ({C}, {num_outputs}) tensor, got {tuple(out.shape)}")
+    num_outputs, out = _chain_prepare(x, taps, decimation, num_outputs, out, fm, odt, channels=C)
     fa = (ctypes.c_float * max(C, 1))(*chans)
     args = [fs, tune, fa]
     if fm:
         args.append((ctypes.c_float * max(C, 1))(*devs))
-    args += [C, decimation, first_sample_index, _ptr(taps), T, 1 if x.dtype == torch.int8 else 0, _ptr(x), _ptr(out),
-             num_outputs, _dev(x), stream_of(x)]
+    args += [C, decimation, first_sample_index, _ptr(taps), taps.numel(), 1 if x.dtype == torch.int8 else 0, _ptr(x),
+             _ptr(out), num_outputs, _dev(x), stream_of(x)]
     check(name, getattr(lib, name)(*args))
     return out
 

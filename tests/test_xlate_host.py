@@ -1,6 +1,6 @@
 """CPU: the frequency-translating FIR's public surface (gsdr_ext.h gsdrxXlatingFir / Int8 / Multi, stream.h
-GSDRX_STREAM_XLATE) -- declared, exported, bound, and validating its arguments before any device work. No compute
-call is made here."""
+GSDRX_STREAM_XLATE) -- declared, exported, bound, and its stream validating its arguments before any device work (the
+entry points' own validation table: test_chain_host.py). No compute call is made here."""
 import ctypes
 import os
 import re
@@ -8,7 +8,7 @@ import subprocess
 
 import pytest
 
-from test_abi import HIP_ERROR_INVALID_VALUE, HIP_SUCCESS, declared_symbols
+from test_abi import HIP_ERROR_INVALID_VALUE, declared_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -40,52 +40,6 @@ def test_stream_kind_value():
     from gsdr_amd.stream import KINDS
 
     assert KINDS["xlate"] == 4 and 3 not in KINDS.values()
-
-
-def test_validation_without_device_work(abi):
-    lib = abi.lib
-    null = None
-    dummy = ctypes.c_void_p(16)
-    inf, nan = float("inf"), float("nan")
-    for fn in (lib.gsdrxXlatingFir, lib.gsdrxXlatingFirInt8):
-        # nothing to do: success whatever the other arguments are
-        assert fn(1e6, 0.0, 1e5, 4, 0, null, 127, null, null, 0, 0, null) == HIP_SUCCESS
-        bad = [
-            (1e6, 0.0, 1e5, 0, 0, dummy, 127, dummy, dummy, 16),    # decimation == 0
-            (1e6, 0.0, 1e5, 4, 0, dummy, 127, null, dummy, 16),     # null input
-            (1e6, 0.0, 1e5, 4, 0, dummy, 127, dummy, null, 16),     # null output
-            (1e6, 0.0, 1e5, 4, 0, null, 127, dummy, dummy, 16),     # null taps with numTaps > 0
-            (0.0, 0.0, 1e5, 4, 0, dummy, 127, dummy, dummy, 16),    # sample rate not positive
-            (-1e6, 0.0, 1e5, 4, 0, dummy, 127, dummy, dummy, 16),
-            (inf, 0.0, 1e5, 4, 0, dummy, 127, dummy, dummy, 16),    # ... or not finite
-            (nan, 0.0, 1e5, 4, 0, dummy, 127, dummy, dummy, 16),
-            (1e6, inf, 1e5, 4, 0, dummy, 127, dummy, dummy, 16),    # frequency difference not finite
-            (1e6, 0.0, nan, 4, 0, dummy, 127, dummy, dummy, 16),
-            (1e6, inf, inf, 4, 0, dummy, 127, dummy, dummy, 16),
-        ]
-        for args in bad:
-            assert fn(*args, 0, null) == HIP_ERROR_INVALID_VALUE, args
-    chans = (ctypes.c_float * 2)(1e5, 2e5)
-    multi = lib.gsdrxXlatingFirMulti
-    assert multi(1e6, 0.0, chans, 2, 4, 0, null, 127, 0, null, null, 0, 0, null) == HIP_SUCCESS   # numOutputs == 0
-    assert multi(1e6, 0.0, null, 0, 4, 0, dummy, 127, 0, dummy, dummy, 16, 0, null) == HIP_SUCCESS  # numChannels == 0
-    assert multi(1e6, 0.0, chans, 0, 4, 0, dummy, 127, 1, dummy, dummy, 16, 0, null) == HIP_SUCCESS
-    bad = [
-        (1e6, 0.0, null, 2, 4, 0, dummy, 127, 0, dummy, dummy, 16),    # null channelFrequencies
-        (1e6, 0.0, chans, 2, 4, 0, dummy, 127, 2, dummy, dummy, 16),   # unknown sample formats
-        (1e6, 0.0, chans, 2, 4, 0, dummy, 127, 7, dummy, dummy, 16),
-        (1e6, 0.0, chans, 2, 4, 0, dummy, 127, -1, dummy, dummy, 16),
-        (1e6, 0.0, chans, 2, 0, 0, dummy, 127, 0, dummy, dummy, 16),   # decimation == 0
-        (1e6, 0.0, chans, 2, 4, 0, dummy, 127, 1, null, dummy, 16),    # null input
-        (1e6, 0.0, chans, 2, 4, 0, dummy, 127, 0, dummy, null, 16),    # null output
-        (1e6, 0.0, chans, 2, 4, 0, null, 127, 0, dummy, dummy, 16),    # null taps with numTaps > 0
-        (0.0, 0.0, chans, 2, 4, 0, dummy, 127, 0, dummy, dummy, 16),   # sample rate not positive
-        (1e6, nan, chans, 2, 4, 0, dummy, 127, 1, dummy, dummy, 16),   # frequency difference not finite
-    ]
-    for args in bad:
-        assert multi(*args, 0, null) == HIP_ERROR_INVALID_VALUE, args
-    bad_channel = (ctypes.c_float * 2)(1e5, inf)
-    assert multi(1e6, 0.0, bad_channel, 2, 4, 0, dummy, 127, 0, dummy, dummy, 16, 0, null) == HIP_ERROR_INVALID_VALUE
 
 
 def test_stream_create_validation_without_device_work(abi):
