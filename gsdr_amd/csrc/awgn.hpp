@@ -89,17 +89,9 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
 // The table in LDS as two float planes R and S (all threads of the workgroup; the caller's barrier
 // publishes it): a normal's two loads then land in any registers, where (R, S) pairs had to be shuffled
 // apart for the packed fma of a symbol's two normals (three moves a symbol).
-// (GSDR_AWGN_PAIRS, a probe-build switch: the round-3 (R, S) pairs, one ds_read_b64 a normal.)
-#if defined(GSDR_AWGN_PAIRS) && !defined(GSDR_TUNING_PROBES)
-#error "GSDR_AWGN_PAIRS is a timing probe: probe builds only"
-#endif
 constexpr int kAwgnLdsSize = 3 * 256;  // the table padded to three entries a thread (awgn_store_table)
 struct AwgnLds {
-#ifdef GSDR_AWGN_PAIRS
-  float2 rs[kAwgnLdsSize];
-#else
   float r[kAwgnLdsSize], s[kAwgnLdsSize];
-#endif
 };
 // Entries below kAwgnTailIndex serve only tail components (a < 32 <=> x = 2 a + 1 < 64 <=> index < 6 * 32),
 // whose values the tail extension replaces: their R is NaN in LDS, so a tail component turns its symbol's
@@ -127,25 +119,11 @@ __device__ __forceinline__ void awgn_store_table(AwgnLds& tab, const AwgnRegs& r
     const uint32_t i = threadIdx.x + 256u * k;
     float2 e = r.e[k];
     if (i < kAwgnTailIndex) e.x = __builtin_nanf("");
-#ifdef GSDR_AWGN_PAIRS
-    tab.rs[i] = e;
-#else
     tab.r[i] = e.x;
     tab.s[i] = e.y;
-#endif
   }
 }
-__device__ __forceinline__ float awgn_fma(const AwgnLds& t, uint32_t i, float f) {
-#if defined(GSDR_TUNING_PROBES) && defined(GSDR_AWGN_PROBE_NOGATHER)
-  i = 256u + (threadIdx.x & 63u) + (i & 0x100u);  // timing probe only: conflict-free, no tail entries, wrong noise
-#endif
-#ifdef GSDR_AWGN_PAIRS
-  const float2 e = t.rs[i];
-  return fmaf(e.y, f, e.x);
-#else
-  return fmaf(t.s[i], f, t.r[i]);
-#endif
-}
+__device__ __forceinline__ float awgn_fma(const AwgnLds& t, uint32_t i, float f) { return fmaf(t.s[i], f, t.r[i]); }
 
 // m with its sign flipped where bit 31 of `sgn` is set: one v_bitop3_b32 (m ^ (sgn & 0x80000000))
 __device__ __forceinline__ float awgn_sign(float m, uint32_t sgn) {

@@ -74,6 +74,28 @@ constexpr T ceil_div(T a, T b) {
   return (a + b - 1) / b;
 }
 
+// The symbol modems' launches (qpsk.hip, qpsk256.hip): up to N streams a launch, grid.y = stream; the kernel takes
+// the pointers by value.
+template <int N>
+struct StreamPtrs {
+  const void* in[N];
+  void* out[N];
+};
+
+template <int N>
+inline bool streams_non_null(const StreamPtrs<N>& st, int used) noexcept {
+  for (int s = 0; s < used; ++s) {
+    if (st.in[s] == nullptr || st.out[s] == nullptr) return false;
+  }
+  return true;
+}
+
+// Workgroups of `threads` threads owning `per_thread` symbols each that cover n symbols. In 64 bits:
+// n + per_thread - 1 wraps a uint32_t for n near 2^32 (numSymbols is uint32_t).
+inline uint32_t symbol_blocks(uint32_t n, uint32_t per_thread, uint32_t threads) noexcept {
+  return (uint32_t)ceil_div<uint64_t>(ceil_div<uint64_t>(n, per_thread), threads);
+}
+
 }  // namespace gsdr
 
 // Body wrapper for C-ABI functions: switch device, run `body` (which returns hipError_t), restore.

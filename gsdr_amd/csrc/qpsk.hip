@@ -18,10 +18,7 @@ namespace gsdr {
 constexpr int kQBlock = 256;
 constexpr int kQSym = 16;  // symbols per thread
 
-struct QpskStreams {
-  const void* in[8];
-  void* out[8];
-};
+using QpskStreams = StreamPtrs<8>;
 
 __device__ __forceinline__ float2 qpsk_point(uint32_t s, float a) {
   return make_float2((s & 1u) ? -a : a, (s & 2u) ? -a : a);
@@ -148,13 +145,10 @@ __global__ __launch_bounds__(kQBlock) void k_qpsk_demod(QpskStreams st, uint32_t
 static hipError_t qpsk_launch(bool modulate, const QpskStreams& st, int nstreams, uint32_t n, float a,
                               int32_t device, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  for (int s = 0; s < nstreams; ++s) {
-    if (st.in[s] == nullptr || st.out[s] == nullptr) return hipErrorInvalidValue;
-  }
+  if (!streams_non_null(st, nstreams)) return hipErrorInvalidValue;
   DeviceScope scope(device);
   if (scope.status() != hipSuccess) return scope.status();
-  // in 64 bits: n + kQSym - 1 wraps a uint32_t for n near 2^32 (numSymbols is uint32_t)
-  const uint32_t blocks = (uint32_t)ceil_div<uint64_t>(ceil_div<uint64_t>(n, kQSym), kQBlock);
+  const uint32_t blocks = symbol_blocks(n, kQSym, kQBlock);
   const dim3 grid(blocks, (uint32_t)nstreams);
   if (modulate) {
     k_qpsk_mod<<<grid, dim3(kQBlock), 0, stream>>>(st, n, a);
@@ -176,10 +170,7 @@ using gsdr::QpskStreams;
 
 GSDR_C_LINKAGE hipError_t gsdrQpskModulate(const uint8_t* inputBits, hipFloatComplex* output, uint32_t numSymbols,
                                            float amplitude, int32_t cudaDevice, hipStream_t cudaStream) GSDR_NO_EXCEPT {
-  QpskStreams st{};
-  st.in[0] = inputBits;
-  st.out[0] = output;
-  return gsdr::qpsk_launch(true, st, 1, numSymbols, amplitude, cudaDevice, cudaStream);
+  return gsdr::qpsk_launch(true, {{inputBits}, {output}}, 1, numSymbols, amplitude, cudaDevice, cudaStream);
 }
 
 GSDR_C_LINKAGE hipError_t gsdrQpskModulate4x(const uint8_t* inputBits0, const uint8_t* inputBits1,
@@ -188,24 +179,13 @@ GSDR_C_LINKAGE hipError_t gsdrQpskModulate4x(const uint8_t* inputBits0, const ui
                                              hipFloatComplex* output2, hipFloatComplex* output3, uint32_t numSymbols,
                                              float amplitude, int32_t cudaDevice,
                                              hipStream_t cudaStream) GSDR_NO_EXCEPT {
-  QpskStreams st{};
-  st.in[0] = inputBits0;
-  st.in[1] = inputBits1;
-  st.in[2] = inputBits2;
-  st.in[3] = inputBits3;
-  st.out[0] = output0;
-  st.out[1] = output1;
-  st.out[2] = output2;
-  st.out[3] = output3;
-  return gsdr::qpsk_launch(true, st, 4, numSymbols, amplitude, cudaDevice, cudaStream);
+  return gsdr::qpsk_launch(true, {{inputBits0, inputBits1, inputBits2, inputBits3}, {output0, output1, output2, output3}},
+                           4, numSymbols, amplitude, cudaDevice, cudaStream);
 }
 
 GSDR_C_LINKAGE hipError_t gsdrQpskDemodulate(const hipFloatComplex* input, uint8_t* outputBits, uint32_t numSymbols,
                                              int32_t cudaDevice, hipStream_t cudaStream) GSDR_NO_EXCEPT {
-  QpskStreams st{};
-  st.in[0] = input;
-  st.out[0] = outputBits;
-  return gsdr::qpsk_launch(false, st, 1, numSymbols, 0.0f, cudaDevice, cudaStream);
+  return gsdr::qpsk_launch(false, {{input}, {outputBits}}, 1, numSymbols, 0.0f, cudaDevice, cudaStream);
 }
 
 GSDR_C_LINKAGE hipError_t gsdrQpskDemodulate4x(const hipFloatComplex* input0, const hipFloatComplex* input1,
@@ -213,16 +193,8 @@ GSDR_C_LINKAGE hipError_t gsdrQpskDemodulate4x(const hipFloatComplex* input0, co
                                                uint8_t* outputBits0, uint8_t* outputBits1, uint8_t* outputBits2,
                                                uint8_t* outputBits3, uint32_t numSymbols, int32_t cudaDevice,
                                                hipStream_t cudaStream) GSDR_NO_EXCEPT {
-  QpskStreams st{};
-  st.in[0] = input0;
-  st.in[1] = input1;
-  st.in[2] = input2;
-  st.in[3] = input3;
-  st.out[0] = outputBits0;
-  st.out[1] = outputBits1;
-  st.out[2] = outputBits2;
-  st.out[3] = outputBits3;
-  return gsdr::qpsk_launch(false, st, 4, numSymbols, 0.0f, cudaDevice, cudaStream);
+  return gsdr::qpsk_launch(false, {{input0, input1, input2, input3}, {outputBits0, outputBits1, outputBits2, outputBits3}},
+                           4, numSymbols, 0.0f, cudaDevice, cudaStream);
 }
 
 GSDR_C_LINKAGE hipError_t gsdrQpskModulateTemplated(const uint8_t* inputBits, hipFloatComplex* output,

@@ -2,36 +2,21 @@
 // Replaces reference src/qpsk256.cu (tables :25-71, modulate :74-151, demodulate :154-259,
 // wrappers :262-431; header qpsk256.h:125-230).
 //
-// Tables are built on the host, in float, with exactly the reference's expressions
-// (qpsk256.cu:33-34, 54-56, 64-67), and uploaded per device on the caller's stream. Each workgroup
-// copies the 2 KiB table it needs into LDS, so lookups are LDS reads rather than divergent
-// constant-cache accesses.
-//
-// Demodulation decision: the reference's own rule (qpsk256.cu:171-181), bit for bit -- the first index
-// attaining the minimum of cuCabsf(received - point) over all 256 points, strict '<', initialised to
-// +inf (so a NaN/inf symbol maps to 0). cuCabsf is CUDA cuComplex.h's scaled hypot (ref_cabsf below),
-// with `1 + t*t` contracted to one fma as nvcc does by default. The fast paths rank candidates by the
-// cheaper squared distance s_i = fl(fl(dx*dx) + fl(dy*dy)) of the same rounded differences: when the
-// smallest s beats every other candidate by a relative margin of 2^-18, which is far wider than the
-// combined rounding of s (2^-23) and of cuCabsf (about 4 ulp), the cuCabsf order agrees and that
-// candidate is the reference's answer. Otherwise (a near-tie) the candidates are re-ranked with
-// cuCabsf itself in ascending index order. For the rectangular grid a received point inside
-// |re|,|im| <= 4|a| can only be won by one of the 3 x 3 grid points around its per-axis nearest level
-// (every other point is farther by >= 0.035 a^2); circular tables use per-cell candidate lists;
-// anything else takes the exhaustive cuCabsf search.
+// Tables are built on the host (qpsk256_tables.hpp), in float, with exactly the reference's expressions, and
+// uploaded per device on the caller's stream. Each workgroup copies the 2 KiB table it needs into LDS, so
+// lookups are LDS reads rather than divergent constant-cache accesses. The demodulation decision -- the
+// reference's own rule, bit for bit -- is qpsk256_decide.hpp.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include <algorithm>
-#include <cmath>
-#include <map>
-#include <type_traits>
-#include <vector>
 
 #include "awgn.hpp"
 #include "gsdr/gsdr_ext.h"
 #include "gsdr/qpsk256.h"
 #include "launch.hpp"
+#include "qpsk256_decide.hpp"
+#include "qpsk256_tables.hpp"
 
 namespace gsdr {
 
@@ -41,185 +26,10 @@ constexpr int kCSym = 16;  // symbols per thread
 // [0] rectangular, [1] circular; per device (module globals are per-device copies).
 __constant__ float2 c_qpsk256_tables[2][256];
 
-// Circular table: per-cell candidate lists over a kCellGrid^2 grid covering [-R, R)^2, built on the
-// host by gsdrQpsk256InitConstellation. A point is listed for a cell when its distance to the cell is
-// at most the smallest worst-case distance of any table point over the cell (plus a margin for float
-// rounding), so every point that can win the argmin anywhere in the cell -- ties included -- is on the
-// list, and the argmin over the list in index order is the exhaustive one -- for the squared distance
-// and, with the near-tie re-ranking of the demodulation kernel, for the reference's cuCabsf rule.
-// R == 0 disables the lookup.
-// One 16-bit word per cell: length (bits 12-15) and, for a one-point list, the point itself (bits
-// 0-11), else the offset of the list in `lists` (ascending indices). Neighbouring cells mostly share
-// their lists, which are stored once: the circular table at any amplitude has 2,863 one-point cells
-// and 6,353 longer lists of which 1,078 are distinct (3,293 bytes), so one cell lookup decides 87 % of
-// noisy symbols with a single LDS load and the whole structure is 22.5 KB of LDS.
-constexpr int kCellGrid = 96;
-constexpr int kCellListBytes = 4096;  // 12-bit offsets
-constexpr double kCellSpan = 1.3;  // grid half-width R = 1.3 * max |c|: noisy symbols stay on the grid
-struct alignas(16) CircCells {
-  float R;
-  float inv_cs;  // kCellGrid / (2 R)
-  uint16_t cell[kCellGrid * kCellGrid];
-  uint8_t lists[kCellListBytes];
-};
+// the circular table's candidate lists (qpsk256_tables.hpp), built by gsdrQpsk256InitConstellation
 __device__ CircCells g_circ_cells;
 
-struct C256Streams {
-  const void* in[4];
-  void* out[4];
-};
-
-__device__ __forceinline__ float sqdist(float2 r, float2 c) {
-  const float dx = __fsub_rn(r.x, c.x);
-  const float dy = __fsub_rn(r.y, c.y);
-  return __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
-}
-
-// cuCabsf (CUDA cuComplex.h, called at qpsk256.cu:173, 182): v = max(|a|, |b|), w = min, t = w / v,
-// |z| = v * sqrt(fma(t, t, 1)), v + w when v == 0 or either exceeds FLT_MAX. IEEE division and square
-// root, as nvcc's defaults (-prec-div, -prec-sqrt) give: '/' and __builtin_sqrtf are correctly rounded
-// under HIP's defaults (__fsqrt_rn is not: this toolchain maps it to the ~1-ulp v_sqrt_f32).
-__device__ __forceinline__ float ref_cabsf(float re, float im) {
-  const float a = fabsf(re), b = fabsf(im);
-  const float v = a > b ? a : b;
-  const float w = a > b ? b : a;
-  float t = __fdiv_rn(w, v);
-  t = fmaf(t, t, 1.0f);
-  t = __fmul_rn(v, __builtin_sqrtf(t));
-  if (v == 0.0f || v > 3.402823466e38f || w > 3.402823466e38f) t = __fadd_rn(v, w);
-  return t;
-}
-
-// the reference's distance of received point r to table point c (cuCsubf, then cuCabsf)
-__device__ __forceinline__ float ref_dist(float2 r, float2 c) { return ref_cabsf(__fsub_rn(r.x, c.x), __fsub_rn(r.y, c.y)); }
-
-// fast-path acceptance: every other candidate's squared distance exceeds s_min by 2^-18 relative
-__device__ __forceinline__ float tie_threshold(float smin) { return fmaf(smin, 0x1p-18f, smin); }
-
-__device__ __noinline__ uint32_t demod_exhaustive(const float2* __restrict__ tab, float2 r) {
-  float best = INFINITY;
-  uint32_t idx = 0;
-  for (uint32_t i = 0; i < 256; ++i) {
-    const float d = ref_dist(r, tab[i]);
-    if (d < best) {
-      best = d;
-      idx = i;
-    }
-  }
-  return idx;
-}
-
-__device__ __forceinline__ int nearest_level(float v, float scale) {
-  // level i sits at (i - 7.5) / 7.5 * a  =>  i ~= v * (7.5 / a) + 7.5
-  const float u = fmaf(v, scale, 7.5f);
-  int i = (int)rintf(u);
-  return i < 0 ? 0 : (i > 15 ? 15 : i);
-}
-
-// Rectangular fast path. Table entry 16 i + q is (lx[i], ly[q]) -- the I coordinate depends on i only
-// and the Q coordinate on q only (qpsk256.cu:33-34) -- so every candidate distance is a rounded sum
-// fl(ex[i] + ey[q]) of per-axis squares read from level arrays, bit-identical to sqdist() on the
-// table entries. lxp / lyp are the level arrays padded with +inf at both ends (entry k + 1 = level k),
-// so neighbours outside [0, 15] have infinite distance and never win.
-//
-// The 3 x 3 neighbourhood of the per-axis nearest levels contains the exhaustive argmin for
-// |re|,|im| <= 4|a|. Rounded addition is monotone in each operand, so with a = first argmin of ex and
-// b = first argmin of ey the minimum is dmin = fl(ex[a] + ey[b]), and every other candidate is >= the
-// second-smallest ex plus ey[b], or >= ex[a] plus the second-smallest ey. When both of those exceed
-// dmin by the 2^-18 margin, (a, b) is the reference's answer; otherwise (a near-tie at a decision
-// boundary) the 9 candidates are ranked by cuCabsf in ascending index order with strict '<', as the
-// reference's exhaustive loop does (no point outside the 3 x 3 can be that close). Returns 256 when the
-// symbol needs the exhaustive search (outside |re|,|im| <= 4|a|, or NaN).
-// The near-tie ranking of demod_rect_fast's 3 x 3 candidates by cuCabsf, in ascending index order with
-// strict '<' as the reference's loop. Out of line: it runs for a few symbols in a million, and inlined
-// into each of a thread's 16 unrolled symbols (nine divisions and square roots each) it made the
-// kernel ~60 KB of code.
-__device__ __noinline__ uint32_t demod_rect_tie(float dx0, float dx1, float dx2, float dy0, float dy1, float dy2,
-                                                int i0, int q0) {
-  const float dx[3] = {dx0, dx1, dx2}, dy[3] = {dy0, dy1, dy2};
-  float best = INFINITY;
-  uint32_t idx = 0;
-#pragma unroll
-  for (int di = 0; di < 3; ++di) {
-#pragma unroll
-    for (int dq = 0; dq < 3; ++dq) {
-      // out-of-grid neighbours (padded +inf levels) give an infinite difference and never win
-      const float d = ref_cabsf(dx[di], dy[dq]);
-      if (d < best) {
-        best = d;
-        idx = (uint32_t)((i0 - 1 + di) * 16 + (q0 - 1 + dq));
-      }
-    }
-  }
-  return idx;
-}
-
-typedef float gsdr_f32x2 __attribute__((ext_vector_type(2)));
-
-// floor(v + 0.5) as an integer in one instruction (v_cvt_rpi_i32_f32); the centre of the 3 x 3 neighbourhood.
-// (It differs from rintf only at exact halves, where both nearest levels are in either neighbourhood.)
-__device__ __forceinline__ int cvt_rpi(float v) {
-  int r;
-  asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(v));
-  return r;
-}
-
-// The three per-axis candidates (levels c - 1, c, c + 1 of the padded array lp): squared differences e0..e2
-// (the first two on packed instructions, straight from the two loaded levels), their minimum, median and
-// the first index reaching the minimum.
-struct AxisCand {
-  float d[3], e[3], emin, emed;
-  int arg;
-};
-__device__ __forceinline__ AxisCand axis_cand(const float* __restrict__ lp, float v) {
-  AxisCand c;
-  const gsdr_f32x2 l01 = gsdr_f32x2{lp[0], lp[1]};
-  const gsdr_f32x2 d01 = gsdr_f32x2{v, v} - l01;  // __fsub_rn each: -ffp-contract=off, no fusing
-  const float d2 = v - lp[2];
-  const gsdr_f32x2 e01 = d01 * d01;
-  c.d[0] = d01.x;
-  c.d[1] = d01.y;
-  c.d[2] = d2;
-  c.e[0] = e01.x;
-  c.e[1] = e01.y;
-  c.e[2] = d2 * d2;
-  c.emin = fminf(fminf(c.e[0], c.e[1]), c.e[2]);
-  c.emed = __builtin_amdgcn_fmed3f(c.e[0], c.e[1], c.e[2]);
-  c.arg = c.e[0] == c.emin ? 0 : (c.e[1] == c.emin ? 1 : 2);
-  return c;
-}
-
-__device__ __forceinline__ uint32_t demod_rect_fast(const float* __restrict__ lxp, const float* __restrict__ lyp, float2 r,
-                                                    float lim, float scale) {
-  if (!(fabsf(r.x) <= lim && fabsf(r.y) <= lim)) return 256u;
-  // level i sits at (i - 7.5) / 7.5 * a  =>  i ~= v * (7.5 / a) + 7.5 (both axes in one packed fma)
-  const gsdr_f32x2 u = __builtin_elementwise_fma(gsdr_f32x2{r.x, r.y}, gsdr_f32x2{scale, scale}, gsdr_f32x2{7.5f, 7.5f});
-  const int i0 = min(max(cvt_rpi(u.x), 0), 15);
-  const int q0 = min(max(cvt_rpi(u.y), 0), 15);
-  const AxisCand cx = axis_cand(lxp + i0, r.x), cy = axis_cand(lyp + q0, r.y);
-  const float thr = tie_threshold(__fadd_rn(cx.emin, cy.emin));
-  if (__fadd_rn(cx.emed, cy.emin) > thr && __fadd_rn(cx.emin, cy.emed) > thr) {
-    return (uint32_t)((i0 - 1 + cx.arg) * 16 + (q0 - 1 + cy.arg));
-  }
-  return demod_rect_tie(cx.d[0], cx.d[1], cx.d[2], cy.d[0], cy.d[1], cy.d[2], i0, q0);
-}
-
-// Rectangular decision in ~15 VALU operations, taken when it is provably the reference's answer. u is the symbol's
-// position in level units per axis (level k at u = k up to rounding: < 2^-17 of a level spacing, from scale, the
-// fma and the host-built levels). When the clamped u of both axes is more than kRectMargin from every midpoint
-// between two levels, the nearest level is unambiguous by a margin (in squared distance the runner-up is farther by
-// >= 2^-11 of dmin) that no rounding of the reference's cuCabsf ranking can reverse, so (i, q) is its first argmin.
-// Symbols within the margin of a midpoint (~1e-4 of noisy symbols) or beyond |re|,|im| <= 4|a| (or NaN) return
-// false and take demod_rect_fast's careful path.
-constexpr float kRectMargin = 0x1p-10f;
-__device__ __forceinline__ bool demod_rect_quick(float2 r, float lim, float scale, uint32_t& k) {
-  const gsdr_f32x2 u = __builtin_elementwise_fma(gsdr_f32x2{r.x, r.y}, gsdr_f32x2{scale, scale}, gsdr_f32x2{7.5f, 7.5f});
-  const float tx = __builtin_amdgcn_fmed3f(u.x, 0.0f, 15.0f), ty = __builtin_amdgcn_fmed3f(u.y, 0.0f, 15.0f);
-  const float ix = __builtin_rintf(tx), iy = __builtin_rintf(ty);
-  const gsdr_f32x2 d = gsdr_f32x2{tx, ty} - gsdr_f32x2{ix, iy};
-  k = (uint32_t)ix * 16u + (uint32_t)iy;
-  return fabsf(r.x) <= lim && fabsf(r.y) <= lim && fmaxf(fabsf(d.x), fabsf(d.y)) <= 0.5f - kRectMargin;
-}
+using C256Streams = StreamPtrs<4>;
 
 __device__ __forceinline__ void load_table(float2* lds_tab, uint32_t type) {
   const float2* src = c_qpsk256_tables[type == 0 ? 0 : 1];
@@ -278,10 +88,7 @@ __global__ __launch_bounds__(kCBlock) void k_c256_mod(C256Streams st, uint32_t n
 // (48-byte lane stride) they ran at about half the copy rate, which bound the kernel once the normals
 // were cheap (the write-heavy maps of section 3.6 showed the same).
 constexpr int kAwgnSym = 6;    // symbols per lane per step
-#ifndef GSDR_AWGN_STEPS
-#define GSDR_AWGN_STEPS 3
-#endif
-constexpr int kAwgnSteps = GSDR_AWGN_STEPS;  // steps per workgroup
+constexpr int kAwgnSteps = 3;  // steps per workgroup (1, 2 and 6 measured slower)
 constexpr uint32_t kAwgnWaveSyms = 64u * kAwgnSym;
 constexpr uint32_t kAwgnBlockSyms = kCBlock * kAwgnSym * kAwgnSteps;
 
@@ -293,17 +100,6 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// RECT (GSDR_C256_RECT_LEVELS = 1, a timing switch, off by default): the rectangular table's entry 16 i + q is
-// (lx[i], ly[q]) (qpsk256.cu:33-34), so a symbol's point can be two 4-byte reads from 16-entry level arrays --
-// conflict-free (distinct levels sit in distinct banks, equal ones broadcast) where the gather from the 256-entry
-// table puts up to ~4 lanes of a group on one bank. Measured side by side (profiles/r05_ab_config5.txt): 29.8 us
-// against 28.8 us for the gather. The kernel is VALU-bound (Philox), and the level reads cost ~17 more VALU
-// instructions per lane step (index splits, two address computations) than the bank conflicts cost in LDS time.
-// firstBlk = firstSymbolIndex / 3: with every lane's first symbol a multiple of 6 from the launch's first, its
-// first Philox block is firstBlk + s / 3 (no 64-bit division per lane).
-#ifndef GSDR_C256_RECT_LEVELS
-#define GSDR_C256_RECT_LEVELS 0
-#endif
 // This lane's six symbols of a step as loaded (a 4-byte and a 2-byte load), kept so until the step needs them:
 // nothing waits for the loads before then.
 struct SymRaw {
@@ -322,17 +118,16 @@ struct SymRaw {
 // it writes, from the registers that hold it -- the decision of gsdrQpsk256Demodulate's rectangular kernel on the
 // same float values, bit for bit -- and writes the decisions to `dec`: the round trip in one pass, without reading
 // the 134 MB of noisy symbols back.
-template <int R3, bool RECT, bool SMALL, bool DEMOD = false>
+// firstBlk = firstSymbolIndex / 3: with every lane's first symbol a multiple of 6 from the launch's first, its
+// first Philox block is firstBlk + s / 3 (no 64-bit division per lane).
+template <int R3, bool SMALL, bool DEMOD = false>
 __global__ __launch_bounds__(kCBlock) __attribute__((amdgpu_waves_per_eu(8))) void k_c256_mod_awgn(const uint8_t* __restrict__ in, float2* __restrict__ out,
                                                             uint32_t n, uint32_t type, float sigma, uint64_t seed,
                                                             uint64_t firstBlk, uint8_t* __restrict__ dec = nullptr) {
   __shared__ float2 tab[256];
-  __shared__ float lev[32];  // RECT: lx[0..15], ly[0..15]
   __shared__ AwgnLds ntab;
   __shared__ float4 stage[kCBlock / 64][kAwgnWaveSyms / 2];  // per wave: 384 symbols as 192 float4
-  __shared__ float levp[DEMOD ? 40 : 1];  // DEMOD: the demodulator's padded level arrays (lxp, lyp; k_c256_demod)
-  float* const lxp = levp;
-  float* const lyp = levp + 20;
+  __shared__ float levp[DEMOD ? kRectLevels : 1];  // DEMOD: the demodulator's padded level arrays
   constexpr int NB = R3 == 0 ? 2 : 3;  // Philox blocks touched by six symbols starting at slot R3
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   float4* __restrict__ st = stage[wv];
@@ -366,21 +161,10 @@ __global__ __launch_bounds__(kCBlock) __attribute__((amdgpu_waves_per_eu(8))) vo
   SymRaw raw = load_syms(0);
   awgn_store_table(ntab, treg);
   tab[threadIdx.x] = trow;
-  if constexpr (RECT) {
-    const float2* src = c_qpsk256_tables[0];
-    if (threadIdx.x < 32) lev[threadIdx.x] = threadIdx.x < 16 ? src[threadIdx.x * 16].x : src[threadIdx.x - 16].y;
-  }
   float lim = -1.0f, scale = 0.0f;
-  if constexpr (DEMOD) {
-    const float2* tsrc = c_qpsk256_tables[0];
-    if (threadIdx.x < 18) {
-      const int k = (int)threadIdx.x - 1;
-      lxp[threadIdx.x] = (k < 0 || k > 15) ? INFINITY : tsrc[k * 16].x;
-      lyp[threadIdx.x] = (k < 0 || k > 15) ? INFINITY : tsrc[k].y;
-    }
-    const float a = tsrc[255].x;  // as k_c256_demod<0>: (15 - 7.5) / 7.5 * a == a exactly
-    scale = 7.5f / a;
-    lim = isfinite(scale) ? 4.0f * fabsf(a) : -1.0f;
+  if constexpr (DEMOD) {  // k_c256_demod<0>'s decider
+    rect_fill_levels(levp, c_qpsk256_tables[0]);
+    rect_limits(c_qpsk256_tables[0][255].x, lim, scale);
   }
   __syncthreads();  // publishes the tables
   // DEMOD: k_c256_demod<0>'s decisions of a lane's six noisy symbols (the reference's cuCabsf argmin, bit for
@@ -398,18 +182,12 @@ __global__ __launch_bounds__(kCBlock) __attribute__((amdgpu_waves_per_eu(8))) vo
         float2 r = y[0];
 #pragma unroll
         for (int i = 1; i < kAwgnSym; ++i) r = j == i ? y[i] : r;  // (a select chain: y stays in registers)
-        uint32_t k = demod_rect_fast(lxp, lyp, r, lim, scale);
+        uint32_t k = demod_rect_fast(levp, levp + kRectLyp, r, lim, scale);
         if (k >= 256u) {  // demod_exhaustive's loop, inline: its call (the ABI's saved registers) cost 17 VGPRs
           float best = INFINITY;
           k = 0;
 #pragma unroll 1
-          for (uint32_t i = 0; i < 256; ++i) {
-            const float dd = ref_dist(r, tab[i]);
-            if (dd < best) {
-              best = dd;
-              k = i;
-            }
-          }
+          for (uint32_t i = 0; i < 256; ++i) rank_step(ref_dist(r, tab[i]), i, best, k);
         }
 #pragma unroll
         for (int i = 0; i < kAwgnSym; ++i) d[i] = j == i ? k : d[i];
@@ -433,11 +211,7 @@ __global__ __launch_bounds__(kCBlock) __attribute__((amdgpu_waves_per_eu(8))) vo
 #pragma unroll
       for (int j = 0; j < kAwgnSym; ++j) {
         const float2 g = awgn_slot_main(ntab, w[(R3 + j) / 3], (R3 + j) % 3);
-#if defined(GSDR_TUNING_PROBES) && defined(GSDR_C256_PROBE_NOSYMGATHER)
-        const float2 p = tab[(lane + (sym[j] & 0x80u)) & 255u];  // timing probe only: conflict-free, wrong symbols
-#else
-        const float2 p = RECT ? make_float2(lev[sym[j] >> 4], lev[16 + (sym[j] & 15)]) : tab[sym[j]];
-#endif
+        const float2 p = tab[sym[j]];
         y[j] = make_float2(p.x + sigma * g.x, p.y + sigma * g.y);
       }
     }
@@ -450,7 +224,7 @@ __global__ __launch_bounds__(kCBlock) __attribute__((amdgpu_waves_per_eu(8))) vo
 #pragma unroll
       for (int j = 0; j < kAwgnSym; ++j) {
         const float2 g = awgn_slot(ntab, w[(R3 + j) / 3], (R3 + j) % 3, seed, b0 + (R3 + j) / 3);
-        const float2 p = RECT ? make_float2(lev[sym[j] >> 4], lev[16 + (sym[j] & 15)]) : tab[sym[j]];
+        const float2 p = tab[sym[j]];
         y[j] = make_float2(p.x + sigma * g.x, p.y + sigma * g.y);
       }
     }
@@ -518,10 +292,9 @@ template <int TYPE>
 __global__ __launch_bounds__(kCBlock) void k_c256_demod(C256Streams st, uint32_t n) {
   // the rectangular levels, padded with +inf (demod_rect_fast), at the start of the table's LDS block: their
   // reads then need no base add (ds_read2_b32 offsets reach 1 KB)
-  __shared__ float2 tab_lev[20 + 256];
-  float* const lxp = reinterpret_cast<float*>(tab_lev);
-  float* const lyp = lxp + 20;
-  float2* const tab = tab_lev + 20;
+  __shared__ float2 tab_lev[kRectLevels / 2 + 256];
+  float* const levp = reinterpret_cast<float*>(tab_lev);
+  float2* const tab = tab_lev + kRectLevels / 2;
   // the circular cell lists: an LDS image of g_circ_cells (cell words and the distinct lists)
   __shared__ uint4 ccells[TYPE == 0 ? 1 : sizeof(CircCells) / 16];
   const uint16_t* cword = reinterpret_cast<const CircCells*>(ccells)->cell;
@@ -532,11 +305,7 @@ __global__ __launch_bounds__(kCBlock) void k_c256_demod(C256Streams st, uint32_t
   __shared__ uint16_t cq[TYPE == 0 ? 1 : kCBlock / 64][TYPE == 0 ? 1 : 64 * kCSym];
   const float2* tsrc = c_qpsk256_tables[TYPE];
   for (uint32_t i = threadIdx.x; i < 256; i += kCBlock) tab[i] = tsrc[i];
-  if (TYPE == 0 && threadIdx.x < 18) {
-    const int k = (int)threadIdx.x - 1;
-    lxp[threadIdx.x] = (k < 0 || k > 15) ? INFINITY : tsrc[k * 16].x;
-    lyp[threadIdx.x] = (k < 0 || k > 15) ? INFINITY : tsrc[k].y;
-  }
+  if constexpr (TYPE == 0) rect_fill_levels(levp, tsrc);
   if (TYPE != 0 && g_circ_cells.R > 0.0f) {  // the circular candidate lists, into LDS
     // 16-byte copies, all issued before the first LDS store (22.5 KB: six loads a lane; a per-entry
     // 2-byte copy loop waited on each load in turn and cost ~5 % of the kernel)
@@ -556,10 +325,7 @@ __global__ __launch_bounds__(kCBlock) void k_c256_demod(C256Streams st, uint32_t
   uint8_t* __restrict__ out = reinterpret_cast<uint8_t*>(st.out[blockIdx.y]);
   float lim = -1.0f, scale = 0.0f, cR = 0.0f, inv_cs = 0.0f;
   if constexpr (TYPE == 0) {
-    const float a = tab[255].x;  // rectangular: (15 - 7.5) / 7.5 * a == a exactly
-    scale = 7.5f / a;
-    // the fast path needs a finite, non-zero amplitude (else every symbol takes the exhaustive search)
-    lim = isfinite(scale) ? 4.0f * fabsf(a) : -1.0f;
+    rect_limits(tab[255].x, lim, scale);
   } else {
     cR = g_circ_cells.R;
     inv_cs = g_circ_cells.inv_cs;
@@ -568,61 +334,19 @@ __global__ __launch_bounds__(kCBlock) void k_c256_demod(C256Streams st, uint32_t
     if constexpr (TYPE == 0) {
       uint32_t k;
       if (demod_rect_quick(r, lim, scale, k)) return k;
-      k = demod_rect_fast(lxp, lyp, r, lim, scale);
+      k = demod_rect_fast(levp, levp + kRectLyp, r, lim, scale);
       return k < 256u ? k : demod_exhaustive(tab, r);
     } else {
-      const float fx = (r.x + cR) * inv_cs, fy = (r.y + cR) * inv_cs;
-      if (cR > 0.0f && fx >= 0.0f && fy >= 0.0f && fx < (float)kCellGrid && fy < (float)kCellGrid) {
-        const uint32_t wc = cword[(int)fy * kCellGrid + (int)fx], len = wc >> 12;
-        if (len == 1u) return wc & 0xfffu;  // a one-point cell: no distance needed
-        const uint32_t b = wc & 0xfffu, e = b + len;
-        float best = INFINITY, second = INFINITY;
-        uint32_t idx = 0;
-        // four candidates per step with independent LDS loads; slots past the list end repeat its
-        // last entry (a duplicate of an entry already ranked: skipped for the runner-up)
-        for (uint32_t m = b; m < e; m += 4) {
-          uint32_t k[4];
-          float2 pt[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) k[j] = clists[m + j < e ? m + j : e - 1];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) pt[j] = tab[k[j]];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float d = (j == 0 || m + j < e) ? sqdist(r, pt[j]) : INFINITY;
-            if (d < best) {
-              second = best;
-              best = d;
-              idx = k[j];
-            } else if (d < second) {
-              second = d;
-            }
-          }
-        }
-        if (second > tie_threshold(best)) return idx;
-        // near-tie: the list (ascending indices, every point that can win in the cell) ranked by
-        // cuCabsf with strict '<', as the reference's loop
-        best = INFINITY;
-        idx = 0;
-        for (uint32_t m = b; m < e; ++m) {
-          const uint32_t k = clists[m];
-          const float d = ref_dist(r, tab[k]);
-          if (d < best) {
-            best = d;
-            idx = k;
-          }
-        }
-        return idx;
-      }
+      uint32_t wc;
+      if (circ_cell(cword, cR, inv_cs, r, wc)) return circ_decide(clists, tab, r, wc);
       return demod_exhaustive(tab, r);
     }
   };
   // circular, first step: a cell whose candidate list holds a single point decides the symbol without
   // any distance; false for longer lists and outside the grid
   auto circ_first = [&](float2 r, uint32_t& idx) -> bool {
-    const float fx = (r.x + cR) * inv_cs, fy = (r.y + cR) * inv_cs;
-    if (!(cR > 0.0f && fx >= 0.0f && fy >= 0.0f && fx < (float)kCellGrid && fy < (float)kCellGrid)) return false;
-    const uint32_t wc = cword[(int)fy * kCellGrid + (int)fx];
+    uint32_t wc;
+    if (!circ_cell(cword, cR, inv_cs, r, wc)) return false;
     idx = wc & 0xffu;  // the point of a one-point cell; the low byte of an offset otherwise (overwritten)
     return (wc >> 12) == 1u;
   };
@@ -699,13 +423,10 @@ constexpr uint32_t kCircBlocks = 1024;
 static hipError_t c256_launch(bool modulate, const C256Streams& st, int nstreams, uint32_t n, uint32_t type,
                               int32_t device, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  for (int s = 0; s < nstreams; ++s) {
-    if (st.in[s] == nullptr || st.out[s] == nullptr) return hipErrorInvalidValue;
-  }
+  if (!streams_non_null(st, nstreams)) return hipErrorInvalidValue;
   DeviceScope scope(device);
   if (scope.status() != hipSuccess) return scope.status();
-  // in 64 bits: n + kCSym - 1 wraps a uint32_t for n near 2^32 (numSymbols is uint32_t)
-  const uint32_t blocks = (uint32_t)ceil_div<uint64_t>(ceil_div<uint64_t>(n, kCSym), kCBlock);
+  const uint32_t blocks = symbol_blocks(n, kCSym, kCBlock);
   const dim3 grid(blocks, (uint32_t)nstreams);
   if (modulate) {
     k_c256_mod<<<grid, dim3(kCBlock), 0, stream>>>(st, n, type);
@@ -722,93 +443,7 @@ static hipError_t c256_launch(bool modulate, const C256Streams& st, int nstreams
   return launch_status();
 }
 
-static constexpr float kPiF = 3.14159265358979323846f;
-
-// Host construction, float arithmetic in the reference's evaluation order.
-static void build_table(uint32_t type, float amplitude, float2* t) {
-  if (type == 0) {
-    for (int i = 0; i < 16; ++i) {
-      for (int q = 0; q < 16; ++q) {
-        const float I = ((float)i - 7.5f) / 7.5f * amplitude;
-        const float Q = ((float)q - 7.5f) / 7.5f * amplitude;
-        t[i * 16 + q] = make_float2(I, Q);
-      }
-    }
-    return;
-  }
-  static const int kPoints[8] = {1, 8, 16, 24, 32, 40, 48, 56};
-  static const float kRadii[8] = {0.0f, 0.3f, 0.6f, 0.85f, 1.1f, 1.35f, 1.6f, 1.85f};
-  int idx = 0;
-  for (int c = 0; c < 8 && idx < 256; ++c) {
-    const int points = kPoints[c] < 256 - idx ? kPoints[c] : 256 - idx;
-    const float radius = kRadii[c] * amplitude;
-    for (int p = 0; p < points && idx < 256; ++p) {
-      const float angle = 2.0f * kPiF * (float)p / (float)points + ((float)c * 0.5f);
-      t[idx++] = make_float2(radius * cosf(angle), radius * sinf(angle));
-    }
-  }
-  while (idx < 256) {
-    const float angle = 2.0f * kPiF * (float)idx / 256.0f;
-    const float radius = amplitude * 0.95f;
-    t[idx] = make_float2(radius * cosf(angle), radius * sinf(angle));
-    ++idx;
-  }
-}
-
-// Candidate lists for the circular table (see CircCells). Distances in double on the float table.
-static bool build_cells(const float2* t, CircCells* cc) {
-  double rmax = 0.0;
-  for (int i = 0; i < 256; ++i) rmax = std::max(rmax, std::hypot((double)t[i].x, (double)t[i].y));
-  cc->R = 0.0f;
-  if (!(rmax > 0.0) || !std::isfinite(rmax)) return true;  // degenerate table: exhaustive search
-  const float R = (float)(rmax * kCellSpan);
-  const float inv_cs = (float)kCellGrid / (2.0f * R);
-  const double cs = 1.0 / (double)inv_cs;
-  const double margin = 1e-4 * rmax;  // >> float rounding of positions and distances
-  int n = 0;
-  std::map<std::vector<uint8_t>, int> seen;  // distinct lists -> offset
-  std::vector<uint8_t> list;
-  for (int iy = 0; iy < kCellGrid; ++iy) {
-    for (int ix = 0; ix < kCellGrid; ++ix) {
-      const double x0 = -(double)R + ix * cs, x1 = x0 + cs, y0 = -(double)R + iy * cs, y1 = y0 + cs;
-      double bound2 = INFINITY;  // smallest worst-case squared distance of a point over the cell
-      for (int q = 0; q < 256; ++q) {
-        const double dx = std::max(std::fabs(t[q].x - x0), std::fabs(t[q].x - x1));
-        const double dy = std::max(std::fabs(t[q].y - y0), std::fabs(t[q].y - y1));
-        bound2 = std::min(bound2, dx * dx + dy * dy);
-      }
-      const double bound = std::sqrt(bound2) + margin;
-      const double lim2 = bound * bound;
-      list.clear();
-      for (int p = 0; p < 256; ++p) {
-        const double dx = std::max({x0 - t[p].x, 0.0, t[p].x - x1});
-        const double dy = std::max({y0 - t[p].y, 0.0, t[p].y - y1});
-        if (dx * dx + dy * dy <= lim2) list.push_back((uint8_t)p);
-      }
-      const int len = (int)list.size();  // >= 1: the point defining the bound is always listed
-      if (len < 1 || len > 15) return true;  // does not fit the cell word: keep the exhaustive search
-      int field = list[0];
-      if (len > 1) {
-        auto it = seen.find(list);
-        if (it == seen.end()) {
-          if (n + len > kCellListBytes) return true;  // does not fit: keep the exhaustive search
-          std::copy(list.begin(), list.end(), cc->lists + n);
-          it = seen.emplace(list, n).first;
-          n += len;
-        }
-        field = it->second;
-      }
-      cc->cell[iy * kCellGrid + ix] = (uint16_t)((len << 12) | field);
-    }
-  }
-  cc->R = R;
-  cc->inv_cs = inv_cs;
-  return true;
-}
-
 }  // namespace gsdr
-
-using gsdr::C256Streams;
 
 GSDR_C_LINKAGE hipError_t gsdrQpsk256InitConstellation(uint32_t constellationType, float amplitude,
                                                        int32_t cudaDevice, hipStream_t cudaStream) GSDR_NO_EXCEPT {
@@ -840,10 +475,7 @@ GSDR_C_LINKAGE hipError_t gsdrQpsk256Modulate(const uint8_t* inputBytes, hipFloa
                                               float amplitude, uint32_t constellationType, int32_t cudaDevice,
                                               hipStream_t cudaStream) GSDR_NO_EXCEPT {
   (void)amplitude;  // scale is fixed by InitConstellation, as in the reference (qpsk256.cu:74-101)
-  C256Streams st{};
-  st.in[0] = inputBytes;
-  st.out[0] = output;
-  return gsdr::c256_launch(true, st, 1, numSymbols, constellationType, cudaDevice, cudaStream);
+  return gsdr::c256_launch(true, {{inputBytes}, {output}}, 1, numSymbols, constellationType, cudaDevice, cudaStream);
 }
 
 namespace gsdr {
@@ -855,41 +487,17 @@ static hipError_t mod_awgn_launch(const uint8_t* inputBytes, hipFloatComplex* ou
   const uint32_t blocks = (uint32_t)ceil_div<uint64_t>(numSymbols, kAwgnBlockSyms);
   float2* out = reinterpret_cast<float2*>(output);
   const uint64_t blk = firstSymbolIndex / 3u;
-  auto launch = [&](auto r3, auto rect, auto demod) {
-    constexpr int R3 = decltype(r3)::value;
-    constexpr bool RECT = decltype(rect)::value, DEMOD = decltype(demod)::value;
-    if (numSymbols < (uint32_t)kAwgnSym) {
-      k_c256_mod_awgn<R3, RECT, true, DEMOD><<<dim3(blocks), dim3(kCBlock), 0, cudaStream>>>(
-          inputBytes, out, numSymbols, constellationType, sigma, seed, blk, dec);
-    } else {
-      k_c256_mod_awgn<R3, RECT, false, DEMOD><<<dim3(blocks), dim3(kCBlock), 0, cudaStream>>>(
-          inputBytes, out, numSymbols, constellationType, sigma, seed, blk, dec);
-    }
-  };
-  auto by_type = [&](auto r3) {
-    if (dec != nullptr) {
-      launch(r3, std::false_type{}, std::true_type{});
-    } else if constexpr (GSDR_C256_RECT_LEVELS != 0) {
-      if (constellationType == 0) {
-        launch(r3, std::true_type{}, std::false_type{});
-      } else {
-        launch(r3, std::false_type{}, std::false_type{});
-      }
-    } else {
-      launch(r3, std::false_type{}, std::false_type{});
-    }
-  };
-  switch (firstSymbolIndex % 3u) {
-    case 0:
-      by_type(std::integral_constant<int, 0>{});
-      break;
-    case 1:
-      by_type(std::integral_constant<int, 1>{});
-      break;
-    default:
-      by_type(std::integral_constant<int, 2>{});
-      break;
-  }
+  using Kernel = void (*)(const uint8_t*, float2*, uint32_t, uint32_t, float, uint64_t, uint64_t, uint8_t*);
+  static constexpr Kernel kKernels[2][3][2] = {  // [DEMOD][R3][SMALL]
+      {{k_c256_mod_awgn<0, false, false>, k_c256_mod_awgn<0, true, false>},
+       {k_c256_mod_awgn<1, false, false>, k_c256_mod_awgn<1, true, false>},
+       {k_c256_mod_awgn<2, false, false>, k_c256_mod_awgn<2, true, false>}},
+      {{k_c256_mod_awgn<0, false, true>, k_c256_mod_awgn<0, true, true>},
+       {k_c256_mod_awgn<1, false, true>, k_c256_mod_awgn<1, true, true>},
+       {k_c256_mod_awgn<2, false, true>, k_c256_mod_awgn<2, true, true>}}};
+  const Kernel kernel = kKernels[dec != nullptr][firstSymbolIndex % 3u][numSymbols < (uint32_t)kAwgnSym];
+  kernel<<<dim3(blocks), dim3(kCBlock), 0, cudaStream>>>(inputBytes, out, numSymbols, constellationType, sigma, seed, blk,
+                                                         dec);
   return launch_status();
 }
 }  // namespace gsdr
@@ -933,10 +541,7 @@ GSDR_C_LINKAGE hipError_t gsdrxQpsk256ModulateAwgnDemodulate(const uint8_t* inpu
 GSDR_C_LINKAGE hipError_t gsdrQpsk256Demodulate(const hipFloatComplex* input, uint8_t* outputBytes,
                                                 uint32_t numSymbols, uint32_t constellationType, int32_t cudaDevice,
                                                 hipStream_t cudaStream) GSDR_NO_EXCEPT {
-  C256Streams st{};
-  st.in[0] = input;
-  st.out[0] = outputBytes;
-  return gsdr::c256_launch(false, st, 1, numSymbols, constellationType, cudaDevice, cudaStream);
+  return gsdr::c256_launch(false, {{input}, {outputBytes}}, 1, numSymbols, constellationType, cudaDevice, cudaStream);
 }
 
 GSDR_C_LINKAGE hipError_t gsdrQpsk256Modulate4x(const uint8_t* inputBytes0, const uint8_t* inputBytes1,
@@ -946,16 +551,8 @@ GSDR_C_LINKAGE hipError_t gsdrQpsk256Modulate4x(const uint8_t* inputBytes0, cons
                                                 uint32_t numSymbols, float amplitude, uint32_t constellationType,
                                                 int32_t cudaDevice, hipStream_t cudaStream) GSDR_NO_EXCEPT {
   (void)amplitude;
-  C256Streams st{};
-  st.in[0] = inputBytes0;
-  st.in[1] = inputBytes1;
-  st.in[2] = inputBytes2;
-  st.in[3] = inputBytes3;
-  st.out[0] = output0;
-  st.out[1] = output1;
-  st.out[2] = output2;
-  st.out[3] = output3;
-  return gsdr::c256_launch(true, st, 4, numSymbols, constellationType, cudaDevice, cudaStream);
+  return gsdr::c256_launch(true, {{inputBytes0, inputBytes1, inputBytes2, inputBytes3}, {output0, output1, output2, output3}},
+                           4, numSymbols, constellationType, cudaDevice, cudaStream);
 }
 
 GSDR_C_LINKAGE hipError_t gsdrQpsk256Demodulate4x(const hipFloatComplex* input0, const hipFloatComplex* input1,
@@ -964,14 +561,7 @@ GSDR_C_LINKAGE hipError_t gsdrQpsk256Demodulate4x(const hipFloatComplex* input0,
                                                   uint8_t* outputBytes3, uint32_t numSymbols,
                                                   uint32_t constellationType, int32_t cudaDevice,
                                                   hipStream_t cudaStream) GSDR_NO_EXCEPT {
-  C256Streams st{};
-  st.in[0] = input0;
-  st.in[1] = input1;
-  st.in[2] = input2;
-  st.in[3] = input3;
-  st.out[0] = outputBytes0;
-  st.out[1] = outputBytes1;
-  st.out[2] = outputBytes2;
-  st.out[3] = outputBytes3;
-  return gsdr::c256_launch(false, st, 4, numSymbols, constellationType, cudaDevice, cudaStream);
+  return gsdr::c256_launch(false, {{input0, input1, input2, input3},
+                                   {outputBytes0, outputBytes1, outputBytes2, outputBytes3}},
+                           4, numSymbols, constellationType, cudaDevice, cudaStream);
 }

@@ -46,6 +46,8 @@ def load(path):
 
 def main():
     libs = [os.path.join(ROOT, "gsdr_amd", "libgsdr.so")] + sys.argv[1:]
+    if os.environ.get("TREE_LAST") == "1":  # a second session with the order swapped: the working tree's library last
+        libs = libs[1:] + libs[:1]
     L = [load(x) for x in libs]
     dev = torch.device("cuda", 0)
     st = torch.cuda.current_stream(dev).cuda_stream
