@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "gsdr/iir.h"
 #include "iir_plan.hpp"
@@ -150,25 +151,7 @@ __device__ __forceinline__ void wave_scan(V (&io)[P], int r, const double* __res
   for (int i = 0; i < P; ++i) io[i] = v[i];
 }
 
-// Column t of M_0, the transition over one chunk: the state after kChunk steps of the homogeneous recursion
-// y[n] = -sum a[i] y[n-i] from e_t. The setup tables (iir_setup) and the fused tails pass's powers (build_pow)
-// both grow from this one function, so they hold the same doubles.
-template <int P>
-__device__ __forceinline__ void chunk_transition_column(const Coeffs& cf, int t, double (&m)[P]) {
-  double am[P + 1];
-#pragma unroll
-  for (int i = 0; i <= P; ++i) am[i] = -coeff(cf.a, cf.K, i);
-#pragma unroll
-  for (int i = 0; i < P; ++i) m[i] = i == t ? 1.0 : 0.0;
-  for (int k = 0; k < kChunk; ++k) {
-    double acc = 0.0;
-#pragma unroll
-    for (int i = 1; i <= P; ++i) acc = fma(am[i], m[i - 1], acc);
-#pragma unroll
-    for (int i = P - 1; i > 0; --i) m[i] = m[i - 1];
-    m[0] = acc;
-  }
-}
+#include "iir_tile.hpp"  // the chunk pass's pieces, shared with the single-pass kernel (iir_resident.hpp)
 
 // One workgroup prepares the scan's constants:
 //   s0        = entry state (double) from the caller's output history, zero-padded to P;
@@ -244,19 +227,11 @@ __device__ __forceinline__ void iir_setup(const Coeffs& cf, const S* __restrict_
   }
 }
 
-// Workgroup of WG threads = WG consecutive chunks = one tile of WG * kChunk samples, staged through
-// LDS so HBM sees coalesced loads/stores; thread t runs the recursion over its chunk from the tile
-// (chunk stride kChunk + 1 elements: consecutive lanes land on different banks).
+// the scan's chunk-pass tile (iir_tile.hpp): 128 threads
 template <class S>
-struct TileShape {
-  static constexpr int WG = 128;
-  static constexpr int NC = sizeof(S) / sizeof(float);  // components per sample: one lane each
-  static constexpr int CPW = WG / NC;                     // chunks per workgroup
-  static constexpr int TS = CPW * kChunk;                 // samples per tile: 33 KB of LDS either way
-  static_assert(TS * sizeof(S) == kTileSampleBytes, "the plan counts these tiles");
-  static constexpr int STRIDE = kChunk + 1;
-  __device__ static int at(int idx) { return idx + idx / kChunk; }
-};
+using ScanTile = TileLayout<S, 128>;
+static_assert(ScanTile<float>::TS * sizeof(float) == kTileSampleBytes, "the plan counts these tiles");
+static_assert(ScanTile<float2>::TS * sizeof(float2) == kTileSampleBytes, "the plan counts these tiles");
 
 enum ChunkPass : int { kTails = 0, kFinal = 1 };
 
@@ -309,24 +284,10 @@ constexpr bool kTableInLds = kGroup * P * P * sizeof(double) <= 32 * 1024;
 
 // Level-0 scan fused into the chunk passes (P <= kFusedMaxP): the tails pass runs the up-sweep of its
 // own groups from LDS (no tails round trip through HBM, no separate launch) and the final pass
-// derives each chunk's start state itself (the level-0 down-sweep). IIR_FUSED_MAXP=0 at build time
-// gives the unfused form (two more launches), kept for side-by-side measurement.
-#ifndef IIR_FUSED_MAXP
-#define IIR_FUSED_MAXP 8
-#endif
-constexpr int kFusedMaxP = IIR_FUSED_MAXP;
-// Ablation probes for timing only (wrong results; never set in the product build): IIR_PROBE_TAILS bits
-// 1 = no transition powers, 2 = no level-0 up-sweep, 4 = no recursion in the tails pass; IIR_PROBE_FINAL
-// bits 1 = no start-state prologue, 2 = no recursion in the final pass.
-#ifndef IIR_PROBE_TAILS
-#define IIR_PROBE_TAILS 0
-#endif
-#ifndef IIR_PROBE_FINAL
-#define IIR_PROBE_FINAL 0
-#endif
-#if (IIR_PROBE_TAILS || IIR_PROBE_FINAL) && !defined(GSDR_TUNING_PROBES)
-#error "IIR_PROBE_TAILS / IIR_PROBE_FINAL produce wrong results (timing ablations): probe builds only"
-#endif
+// derives each chunk's start state itself (the level-0 down-sweep). P > kFusedMaxP (K > 9) runs the unfused
+// passes: level 0 as launches of its own (k_iir_up / k_iir_down, or k_iir_scan_rest), tails and start states
+// through HBM.
+constexpr int kFusedMaxP = 8;
 
 // Up-sweep of group g of one level (one wave, lane r = element j = g*64 + r, read from mine[0 .. P): the level's
 // elements in global memory, or the workgroup's tails in LDS for the fused level 0). Lane r's result, the zero-state
@@ -350,23 +311,27 @@ __device__ __forceinline__ void up_group(const A* __restrict__ mine, uint64_t E,
   }
 }
 
+// One chunk pass of the scan. Its staging, previous inputs, recursion and store are the operations of iir_tile.hpp's
+// stage_tile / prev_inputs / run_chunk / store_tile, written out here: through those functions the compiler scheduled
+// every instantiation differently and three of eight timed calls got slower (iir_tile.hpp).
 template <class S, int P, int PASS, bool VEC, bool FUSED = false>
-__global__ __launch_bounds__(TileShape<S>::WG) void k_iir_chunks(Coeffs cf, const S* __restrict__ x,
+__global__ __launch_bounds__(ScanTile<S>::WG) void k_iir_chunks(Coeffs cf, const S* __restrict__ x,
                                                                  const S* __restrict__ xh, uint64_t n,
                                                                  PassArgs<S, PASS, FUSED> pa) {
-  using TSh = TileShape<S>;
+  using TSh = ScanTile<S>;
   using A = typename Acc<S>::type;
-  constexpr size_t kTileBytes = sizeof(S) * TSh::CPW * TSh::STRIDE;
+  constexpr size_t kTileBytes = TSh::kBytes;
   constexpr size_t kTableBytes = kTableInLds<P> ? kGroup * P * P * sizeof(double) : 0;
   __shared__ __attribute__((aligned(16))) char smem[kTileBytes > kTableBytes ? kTileBytes : kTableBytes];
   // fused tails pass: M_0^(2^s), s < 6, and the workgroup's chunk tails
   constexpr int kPow = (FUSED && PASS == kTails) ? 6 * P * P : 1;
-  static_assert(!FUSED || TSh::CPW * P * sizeof(A) <= kTileBytes, "tails alias the tile");
+  static_assert(!FUSED || TSh::CPT * P * sizeof(A) <= kTileBytes, "tails alias the tile");
   __shared__ double mpow[kPow];
   __shared__ S pre[P];  // x[base - 1 - i], i < P
   S* tile = reinterpret_cast<S*>(smem);
   A* tl = reinterpret_cast<A*>(smem);  // fused tails pass: the chunk tails, once the tile is consumed
   const int t = threadIdx.x;
+  // 1. Setup workgroup
   if constexpr (PASS == kTails) {
     // the extra FIRST workgroup builds the scan constants while the others compute the tails (as the
     // last one it was dispatched after most tiles and finished after them: ~7 us at the kernel's end)
@@ -420,15 +385,16 @@ __global__ __launch_bounds__(TileShape<S>::WG) void k_iir_chunks(Coeffs cf, cons
     const uint64_t base = ti * TSh::TS;
     const uint32_t tlen = n - base < (uint64_t)TSh::TS ? (uint32_t)(n - base) : (uint32_t)TSh::TS;
     const bool whole = is_whole(ti);
-    const uint64_t c = ti * TSh::CPW + t / NC;
+    const uint64_t c = ti * TSh::CPT + t / NC;
     const uint64_t n0 = c * kChunk;
     double ys[P];  // component of y[n-1-i]: the chunk's start state
 #pragma unroll
     for (int i = 0; i < P; ++i) ys[i] = 0.0;
+    // 2. Start-state operands
     // Final pass: the operands of the chunk's start state are loaded BEFORE the tile. Vector loads retire
     // in order, so operands loaded after the tile could only be used once the whole tile had arrived: the
     // start state's FMAs would then sit on the critical path instead of under the tile's load latency.
-    constexpr bool kPro = FUSED && PASS == kFinal && !(IIR_PROBE_FINAL & 1);
+    constexpr bool kPro = FUSED && PASS == kFinal;
     constexpr int PP = P * P;
     double mr[kPro ? PP : 1], inc[kPro ? P : 1], sgc[kPro ? P : 1];
     const uint64_t g = c / kGroup;
@@ -447,12 +413,13 @@ __global__ __launch_bounds__(TileShape<S>::WG) void k_iir_chunks(Coeffs cf, cons
         for (int l = 0; l < P; ++l) sgc[l] = sg[l * NC + comp];
       }
     }
+    // 3. Tile loads
     float4 v[NV];
     if (whole) load_tile(ti, v);  // in flight while the final pass computes the chunk start state
 
     // the P samples before the tile (the input history for the first tile), loaded beside it
-    S pv = zero_s(S{});
-    if (t < P) pv = x_at(x, xh, cf.K, (int64_t)base - 1 - t);
+    const S pv = load_pre<P>(x, xh, cf.K, base, t);
+    // 4. Start state
     if constexpr (kPro) {
       if (n0 < n) {
 #pragma unroll
@@ -466,6 +433,7 @@ __global__ __launch_bounds__(TileShape<S>::WG) void k_iir_chunks(Coeffs cf, cons
         for (int i = 0; i < P; ++i) ys[i] = starts_d[(c * P + i) * NC + comp];
       }
     }
+    // 5. Stage
     if (whole) {
 #pragma unroll
       for (int k = 0; k < NV; ++k) {
@@ -481,6 +449,7 @@ __global__ __launch_bounds__(TileShape<S>::WG) void k_iir_chunks(Coeffs cf, cons
     }
     if (t < P) pre[t] = pv;
     lds_barrier();
+    // 6. Previous inputs
     // component of x[n-1-i] for every chunk, read before any row is overwritten with y
     double xd[P];
     {
@@ -492,6 +461,7 @@ __global__ __launch_bounds__(TileShape<S>::WG) void k_iir_chunks(Coeffs cf, cons
       }
     }
     if constexpr (PASS == kFinal) lds_barrier();
+    // 7. Recursion
     // lane t runs the recursion of component t % NC of chunk t / NC (complex samples with real
     // coefficients are two independent real recursions): scalar double state, twice the lanes
     if (n0 < n) {
@@ -518,13 +488,13 @@ __global__ __launch_bounds__(TileShape<S>::WG) void k_iir_chunks(Coeffs cf, cons
         ys[0] = acc;
         if constexpr (PASS == kFinal) row[k * NC] = (float)acc;  // y replaces x in this chunk's row
       };
-      if ((PASS == kTails && (IIR_PROBE_TAILS & 4)) || (PASS == kFinal && (IIR_PROBE_FINAL & 2))) {
-      } else if (len == (uint32_t)kChunk) {
+      if (len == (uint32_t)kChunk) {
 #pragma unroll
         for (uint32_t k = 0; k < (uint32_t)kChunk; ++k) step(k);
       } else {
         for (uint32_t k = 0; k < len; ++k) step(k);
       }
+      // 8. Tails (unfused: to HBM), or the history after the final pass's last chunk
       if constexpr (PASS == kTails && !FUSED) {
         double* __restrict__ tails_d = reinterpret_cast<double*>(pa.tails);
 #pragma unroll
@@ -543,8 +513,9 @@ __global__ __launch_bounds__(TileShape<S>::WG) void k_iir_chunks(Coeffs cf, cons
         }
       }
     }
+    // 8, fused: the tails into LDS and the up-sweep of the workgroup's own level-0 groups
     if constexpr (PASS == kTails && FUSED) {
-      if (!(IIR_PROBE_TAILS & 1) && ti == first_ti) build_pow();
+      if (ti == first_ti) build_pow();
       lds_barrier();  // every lane is done reading the tile
       if (n0 < n) {
 #pragma unroll
@@ -552,13 +523,14 @@ __global__ __launch_bounds__(TileShape<S>::WG) void k_iir_chunks(Coeffs cf, cons
       }
       lds_barrier();
       const int w = t / kGroup;
-      if (!(IIR_PROBE_TAILS & 2) && w < TSh::CPW / kGroup) {
+      if (w < TSh::CPT / kGroup) {
         const uint64_t C = (n + kChunk - 1) / kChunk;
-        const uint64_t g = ti * (TSh::CPW / kGroup) + w;
+        const uint64_t g = ti * (TSh::CPT / kGroup) + w;
         const int lane = t % kGroup;
         up_group<A, P, kPackedPow>(tl + (w * kGroup + lane) * P, C, mpow, pa.incl, pa.aggs, g, lane);
       }
     }
+    // 9. Store
     if constexpr (PASS == kFinal) {
       lds_barrier();
       S* __restrict__ y = pa.y;
@@ -742,80 +714,17 @@ __global__ __launch_bounds__(64 * kUpperWaves) void k_iir_scan_upper(uint64_t E1
   }
 }
 
-// Which formulation a call runs: the multi-pass scan below (the product's only path), or -- in the tuning-probe
-// build only -- the single-pass kernel of iir_resident.hpp, chosen per call (gsdrxIirFFSinglePass / CC).
-struct PathSel {
-  bool single_pass = false;
-  uint32_t max_polls = 0;  // the single-pass kernel's bound on every wait
-};
-
-#ifdef GSDR_TUNING_PROBES
-#include "iir_resident.hpp"
-
-// bit 0: a single-pass tile gave up waiting since the last gsdrxIirSinglePassStatus (per device)
-__device__ uint32_t g_res_status;
-
-template <class S, int P>
-static hipError_t run_resident(const Coeffs& cf, S* xh, S* yh, const S* x, S* y, uint64_t n, hipStream_t st,
-                               uint32_t max_polls) {
-  using Sh = res::Shape<S>;
-  constexpr int NC = Sh::NC;
-  const uint64_t ntiles = ceil_div<uint64_t>(n, Sh::TS);
-  const uint64_t nsb = ceil_div<uint64_t>(ntiles, res::kResSB);
-  // one block: the tile aggregates, the superblock aggregates (both filled with kResEmpty by the setup
-  // kernel), the tables and coefficients
-  const uint64_t nagg = (ntiles + nsb) * P * NC;
-  const size_t off_tabs = nagg * sizeof(double);
-  const size_t off_ticket = off_tabs + (res::res_tab_doubles<P>() + res::res_coef_doubles<P>()) * sizeof(double);
-  const size_t bytes = off_ticket + 16;
-  void* status = nullptr;
-  hipError_t se = hipGetSymbolAddress(&status, HIP_SYMBOL(g_res_status));
-  if (se != hipSuccess) return se;
-  char* ws = nullptr;
-  hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&ws), bytes, st);
-  if (e != hipSuccess) return e;
-  res::ResArgs ra{};
-  ra.loc = reinterpret_cast<double*>(ws);
-  ra.sbagg = ra.loc + ntiles * P * NC;
-  double* tabs = reinterpret_cast<double*>(ws + off_tabs);
-  ra.tabs = tabs;
-  ra.xh_out = reinterpret_cast<float*>(xh);
-  ra.yh_out = reinterpret_cast<float*>(yh);
-  ra.Pk = cf.K - 1;
-  ra.ticket = reinterpret_cast<uint32_t*>(ws + off_ticket);
-  ra.status = static_cast<uint32_t*>(status);
-  ra.max_polls = max_polls;
-  const uint32_t nclear = (uint32_t)std::min<uint64_t>(512, ceil_div<uint64_t>(nagg, 8 * res::kResWG));
-  res::k_res_setup<S, P><<<1 + nclear, res::kResWG, 0, st>>>(cf, tabs, reinterpret_cast<uint64_t*>(ws), nagg, ra.ticket);
-  const auto k = aligned16(x) && aligned16(y) ? res::k_iir_resident<S, P, true> : res::k_iir_resident<S, P, false>;
-  k<<<(uint32_t)ntiles, res::kResWG, 0, st>>>(cf, x, xh, yh, n, y, ra);
-  e = launch_status();
-  const hipError_t f = hipFreeAsync(ws, st);
-  return e != hipSuccess ? e : f;
-}
-
-#endif  // GSDR_TUNING_PROBES
-
 // one chunk pass: 16-byte tile loads / stores when the caller's buffers allow them (vec)
 template <class S, int P, int PASS, bool FUSED>
 static void launch_chunks(uint32_t blocks, hipStream_t st, bool vec, const Coeffs& cf, const S* x, const S* xh,
                           uint64_t n, const PassArgs<S, PASS, FUSED>& pa) {
   const auto kernel = vec ? k_iir_chunks<S, P, PASS, true, FUSED> : k_iir_chunks<S, P, PASS, false, FUSED>;
-  kernel<<<blocks, TileShape<S>::WG, 0, st>>>(cf, x, xh, n, pa);
+  kernel<<<blocks, ScanTile<S>::WG, 0, st>>>(cf, x, xh, n, pa);
 }
 
+// the multi-pass scan of one call, state size P
 template <class S, int P>
-static hipError_t run(const Coeffs& cf, S* xh, S* yh, const S* x, S* y, uint64_t n, hipStream_t st, PathSel ps) {
-  if (ps.single_pass) {
-#ifdef GSDR_TUNING_PROBES
-    // K <= 9 and up to 2^16 tiles (2^29 real / 2^28 complex samples); anything else is refused, not rerouted
-    if constexpr (P <= kFusedMaxP) {
-      if (ceil_div<uint64_t>(n, res::Shape<S>::TS) <= res::kResMaxTiles)
-        return run_resident<S, P>(cf, xh, yh, x, y, n, st, ps.max_polls);
-    }
-#endif
-    return hipErrorNotSupported;
-  }
+static hipError_t run(const Coeffs& cf, S* xh, S* yh, const S* x, S* y, uint64_t n, hipStream_t st) {
   using A = typename Acc<S>::type;
   constexpr bool F = P <= kFusedMaxP;
   Workspace<A> W{};
@@ -848,9 +757,9 @@ static hipError_t run(const Coeffs& cf, S* xh, S* yh, const S* x, S* y, uint64_t
     k_iir_up<A, P><<<groups(k), 64, 0, st>>>(W.elems(k), pl.E[k], W.table(k), W.starts(k), W.elems(k + 1));
   if constexpr (F) {
     if (pl.upper) {
-      const dim3 grid((uint32_t)ceil_div<uint64_t>(pl.E[2], kUpperWaves), TileShape<S>::NC);
+      const dim3 grid((uint32_t)ceil_div<uint64_t>(pl.E[2], kUpperWaves), ScanTile<S>::NC);
       k_iir_scan_upper<P><<<grid, 64 * kUpperWaves, 0, st>>>(
-          pl.E[1], pl.E[2], TileShape<S>::NC, W.table(1), W.table(2), pl.levels >= 3 ? W.table(3) : nullptr,
+          pl.E[1], pl.E[2], ScanTile<S>::NC, W.table(1), W.table(2), pl.levels >= 3 ? W.table(3) : nullptr,
           reinterpret_cast<const double*>(W.elems(2)), reinterpret_cast<const double*>(s0),
           reinterpret_cast<double*>(W.starts(1)));
     }
@@ -880,9 +789,20 @@ static hipError_t run(const Coeffs& cf, S* xh, S* yh, const S* x, S* y, uint64_t
   return e != hipSuccess ? e : f;
 }
 
+// f(std::integral_constant<int, P>) for the compiled state size P that holds the filter's K - 1
+template <class F>
+static hipError_t dispatch_state_size(size_t Pk, F&& f) {
+  if (Pk <= 1) return f(std::integral_constant<int, 1>{});
+  if (Pk <= 2) return f(std::integral_constant<int, 2>{});
+  if (Pk <= 4) return f(std::integral_constant<int, 4>{});
+  if (Pk <= 8) return f(std::integral_constant<int, 8>{});
+  if (Pk <= 16) return f(std::integral_constant<int, 16>{});
+  return f(std::integral_constant<int, 31>{});
+}
+
 template <class S>
 static hipError_t entry(const float* b, const float* a, size_t K, S* xh, S* yh, const S* x, S* y, size_t n,
-                        int32_t device, hipStream_t st, PathSel ps = {}) {
+                        int32_t device, hipStream_t st) {
   if (K < 2 || K > 32) return hipErrorInvalidValue;  // reference limits (iir.cu:229-235)
   if (n == 0) return hipSuccess;
   if (b == nullptr || a == nullptr || x == nullptr || y == nullptr) return hipErrorInvalidValue;
@@ -890,13 +810,7 @@ static hipError_t entry(const float* b, const float* a, size_t K, S* xh, S* yh, 
   DeviceScope scope(device);
   if (scope.status() != hipSuccess) return scope.status();
   const Coeffs cf{b, a, (int)K};
-  const size_t P = K - 1;
-  if (P <= 1) return run<S, 1>(cf, xh, yh, x, y, n, st, ps);
-  if (P <= 2) return run<S, 2>(cf, xh, yh, x, y, n, st, ps);
-  if (P <= 4) return run<S, 4>(cf, xh, yh, x, y, n, st, ps);
-  if (P <= 8) return run<S, 8>(cf, xh, yh, x, y, n, st, ps);
-  if (P <= 16) return run<S, 16>(cf, xh, yh, x, y, n, st, ps);
-  return run<S, 31>(cf, xh, yh, x, y, n, st, ps);
+  return dispatch_state_size(K - 1, [&](auto p) { return run<S, decltype(p)::value>(cf, xh, yh, x, y, n, st); });
 }
 
 }  // namespace iir
@@ -938,7 +852,77 @@ GSDR_C_LINKAGE hipError_t gsdrIirCCCustom(const float* bCoeffs, const float* aCo
 }
 
 #ifdef GSDR_TUNING_PROBES
-// Tuning-probe build only (libgsdr_probes.so; tools/ and tests/test_gpu_iir.py bind them by name):
+// Tuning-probe build only (libgsdr_probes.so; tools/ and tests/test_gpu_iir.py bind them by name): the single-pass
+// kernel of iir_resident.hpp beside the scan above, which stays the product's only path.
+namespace gsdr {
+namespace iir {
+#include "iir_resident.hpp"
+
+// bit 0: a single-pass tile gave up waiting since the last gsdrxIirSinglePassStatus (per device)
+__device__ uint32_t g_res_status;
+
+template <class S, int P>
+static hipError_t run_resident(const Coeffs& cf, S* xh, S* yh, const S* x, S* y, uint64_t n, hipStream_t st,
+                               uint32_t max_polls) {
+  constexpr int NC = res::Tile<S>::NC;
+  const uint64_t ntiles = ceil_div<uint64_t>(n, res::Tile<S>::TS);
+  const uint64_t nsb = ceil_div<uint64_t>(ntiles, res::kResSB);
+  // one block: the tile aggregates, the superblock aggregates (both filled with kResEmpty by the setup
+  // kernel), the tables and coefficients
+  const uint64_t nagg = (ntiles + nsb) * P * NC;
+  const size_t off_tabs = nagg * sizeof(double);
+  const size_t off_ticket = off_tabs + (res::res_tab_doubles<P>() + res::res_coef_doubles<P>()) * sizeof(double);
+  const size_t bytes = off_ticket + 16;
+  void* status = nullptr;
+  hipError_t se = hipGetSymbolAddress(&status, HIP_SYMBOL(g_res_status));
+  if (se != hipSuccess) return se;
+  char* ws = nullptr;
+  hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&ws), bytes, st);
+  if (e != hipSuccess) return e;
+  res::ResArgs ra{};
+  ra.loc = reinterpret_cast<double*>(ws);
+  ra.sbagg = ra.loc + ntiles * P * NC;
+  double* tabs = reinterpret_cast<double*>(ws + off_tabs);
+  ra.tabs = tabs;
+  ra.xh_out = reinterpret_cast<float*>(xh);
+  ra.yh_out = reinterpret_cast<float*>(yh);
+  ra.Pk = cf.K - 1;
+  ra.ticket = reinterpret_cast<uint32_t*>(ws + off_ticket);
+  ra.status = static_cast<uint32_t*>(status);
+  ra.max_polls = max_polls;
+  const uint32_t nclear = (uint32_t)std::min<uint64_t>(512, ceil_div<uint64_t>(nagg, 8 * res::kResWG));
+  res::k_res_setup<S, P><<<1 + nclear, res::kResWG, 0, st>>>(cf, tabs, reinterpret_cast<uint64_t*>(ws), nagg, ra.ticket);
+  const auto k = aligned16(x) && aligned16(y) ? res::k_iir_resident<S, P, true> : res::k_iir_resident<S, P, false>;
+  k<<<(uint32_t)ntiles, res::kResWG, 0, st>>>(cf, x, xh, yh, n, y, ra);
+  e = launch_status();
+  const hipError_t f = hipFreeAsync(ws, st);
+  return e != hipSuccess ? e : f;
+}
+
+// entry()'s checks in entry()'s order, then the single-pass kernel: K <= 9 and up to 2^16 tiles (2^29 real / 2^28
+// complex samples); anything else is refused, not rerouted
+template <class S>
+static hipError_t entry_single_pass(const float* b, const float* a, size_t K, S* xh, S* yh, const S* x, S* y, size_t n,
+                                    uint32_t max_polls, int32_t device, hipStream_t st) {
+  if (K < 2 || K > 32) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  if (b == nullptr || a == nullptr || x == nullptr || y == nullptr) return hipErrorInvalidValue;
+  DeviceScope scope(device);
+  if (scope.status() != hipSuccess) return scope.status();
+  const Coeffs cf{b, a, (int)K};
+  return dispatch_state_size(K - 1, [&](auto p) {
+    constexpr int P = decltype(p)::value;
+    if constexpr (P <= res::kResMaxP) {
+      if (ceil_div<uint64_t>(n, res::Tile<S>::TS) <= res::kResMaxTiles)
+        return run_resident<S, P>(cf, xh, yh, x, y, n, st, max_polls);
+    }
+    return hipErrorNotSupported;
+  });
+}
+
+}  // namespace iir
+}  // namespace gsdr
+
 // gsdrIirFF / gsdrIirCC on the single-pass kernel, chosen per call. maxPolls bounds every wait in polling rounds
 // (2^22 is the measured setting; 0 makes every tile that has to wait give up at once, which is how the status
 // path is tested); hipErrorNotSupported for K > 9 or more than 2^16 tiles. A give-up is reported by
@@ -949,9 +933,8 @@ GSDR_PROBE_API hipError_t gsdrxIirFFSinglePass(const float* bCoeffs, const float
                                                float* inputHistory, float* outputHistory, const float* input,
                                                float* output, size_t numElements, uint32_t maxPolls,
                                                int32_t cudaDevice, hipStream_t cudaStream) noexcept {
-  return gsdr::iir::entry<float>(bCoeffs, aCoeffs, coeffCount, inputHistory, outputHistory, input, output,
-                                 numElements, cudaDevice, cudaStream,
-                                 gsdr::iir::PathSel{true, maxPolls});
+  return gsdr::iir::entry_single_pass<float>(bCoeffs, aCoeffs, coeffCount, inputHistory, outputHistory, input, output,
+                                             numElements, maxPolls, cudaDevice, cudaStream);
 }
 
 GSDR_PROBE_API hipError_t gsdrxIirCCSinglePass(const float* bCoeffs, const float* aCoeffs, size_t coeffCount,
@@ -959,10 +942,10 @@ GSDR_PROBE_API hipError_t gsdrxIirCCSinglePass(const float* bCoeffs, const float
                                                const hipFloatComplex* input, hipFloatComplex* output,
                                                size_t numElements, uint32_t maxPolls, int32_t cudaDevice,
                                                hipStream_t cudaStream) noexcept {
-  return gsdr::iir::entry<float2>(bCoeffs, aCoeffs, coeffCount, reinterpret_cast<float2*>(inputHistory),
-                                  reinterpret_cast<float2*>(outputHistory), reinterpret_cast<const float2*>(input),
-                                  reinterpret_cast<float2*>(output), numElements, cudaDevice, cudaStream,
-                                  gsdr::iir::PathSel{true, maxPolls});
+  return gsdr::iir::entry_single_pass<float2>(
+      bCoeffs, aCoeffs, coeffCount, reinterpret_cast<float2*>(inputHistory), reinterpret_cast<float2*>(outputHistory),
+      reinterpret_cast<const float2*>(input), reinterpret_cast<float2*>(output), numElements, maxPolls, cudaDevice,
+      cudaStream);
 }
 
 // hipSuccess when no single-pass tile gave up since the last query, else hipErrorLaunchFailure
@@ -981,4 +964,4 @@ GSDR_PROBE_API hipError_t gsdrxIirSinglePassStatus(int32_t cudaDevice, hipStream
   if (e == hipSuccess) e = hipStreamSynchronize(cudaStream);
   return e != hipSuccess ? e : hipErrorLaunchFailure;
 }
-#endif
+#endif  // GSDR_TUNING_PROBES

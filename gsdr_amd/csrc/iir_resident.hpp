@@ -18,8 +18,9 @@
 //      Hillis-Steele trees, so the result does not depend on timing) and composes
 //        S_tile = M_T^k S_sb + U_(k-1),  S_sb = M_SB^sb s0 + Q_(sb-1)
 //      (k = its index in the superblock, U / Q the inclusive scans, M_T = M0^(chunks a tile), M_SB = M_T^256);
-//   4. every chunk starts from M0^e S_tile + prefix_(e-1), the recursion re-runs over the staged tile and y leaves
-//      through LDS in coalesced rows.
+//   4. every chunk starts from M0^e S_tile + prefix_(e-1); its free response from that state (the table gk) is added
+//      to the zero-state outputs in the staged tile, without a second recursion, and y leaves through LDS in
+//      coalesced rows.
 // Tile numbers come from an atomic ticket taken when a workgroup starts, so a workgroup waits only on tiles
 // whose workgroups are already running: the waits cannot deadlock whatever order the hardware dispatches the
 // grid in. Every wait is bounded (ResArgs::max_polls rounds): a tile that gives up records it in the device
@@ -33,17 +34,14 @@ namespace res {
 constexpr int kResWG = 256;
 constexpr uint32_t kResSB = 256;        // tiles per superblock
 constexpr uint32_t kResMaxTiles = 256 * kResSB;
+constexpr int kResMaxP = 8;             // K <= 9
 
+// the single pass's tile (iir_tile.hpp): 256 threads, 256 rows of 33 floats
 template <class S>
-struct Shape {
-  static constexpr int NC = sizeof(S) / sizeof(float);   // components (one lane each)
-  static constexpr int CPT = kResWG / NC;                 // chunks a tile
-  static constexpr int TS = CPT * kChunk;                 // samples a tile
-  static constexpr int LOGCPT = NC == 1 ? 8 : 7;
-  static constexpr int STRIDE = kChunk + 1;               // LDS row stride (floats of one component)
-  static constexpr size_t kTileFloats = (size_t)kResWG * STRIDE;  // 256 rows of 33 floats
-  __device__ static int at(int idx) { return idx + idx / kChunk; }  // sample idx -> padded slot (in S units)
-};
+using Tile = TileLayout<S, kResWG>;
+template <class S>
+constexpr int kLogCpt = Tile<S>::NC == 1 ? 8 : 7;  // M_T = M0^(2^kLogCpt)
+static_assert((1 << kLogCpt<float>) == Tile<float>::CPT && (1 << kLogCpt<float2>) == Tile<float2>::CPT, "chunks a tile");
 
 struct ResArgs {
   double* loc;       // [tile][P][NC]: tile aggregates (zero entry), kResEmpty until written
@@ -62,22 +60,20 @@ struct ResArgs {
 // acquire / release write back and invalidate the whole L2 of the XCD; with hundreds of polls a tile that cost
 // more than the filter. So there are no flags: the setup kernel fills the aggregate arrays with kResEmpty (a
 // signalling NaN whose low payload bits no float input or arithmetic result can carry), a workgroup writes its
-// aggregate with relaxed atomic stores at GSDR_RES_SCOPE (system scope by default -- the setting every
-// measurement used; they bypass the non-coherent caching) and a reader polls the values themselves with relaxed
-// atomic loads of the same scope until none is kResEmpty: each 8-byte value is written and read whole, so no
-// value can be seen half-written, and a write needs no fence or completion wait before the writer moves on.
+// aggregate with relaxed atomic stores at kResScope (system scope -- the setting every measurement used; they bypass
+// the non-coherent caching) and a reader polls the values themselves with relaxed atomic loads of the same scope
+// until none is kResEmpty: each 8-byte value is written and read whole, so no value can be seen half-written, and
+// a write needs no fence or completion wait before the writer moves on.
 constexpr uint64_t kResEmpty = 0x7FF4DEAD5EED1234ull;
-#ifndef GSDR_RES_SCOPE
-#define GSDR_RES_SCOPE __HIP_MEMORY_SCOPE_SYSTEM
-#endif
+constexpr int kResScope = __HIP_MEMORY_SCOPE_SYSTEM;
 
 __device__ __forceinline__ void st_co(double* p, double v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, GSDR_RES_SCOPE);
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, kResScope);
 }
 
-// load one value (GSDR_RES_SCOPE, bypassing the non-coherent caching)
+// load one value (kResScope, bypassing the non-coherent caching)
 __device__ __forceinline__ uint64_t ld_bits(const double* p) {
-  return __hip_atomic_load(reinterpret_cast<const uint64_t*>(p), __ATOMIC_RELAXED, GSDR_RES_SCOPE);
+  return __hip_atomic_load(reinterpret_cast<const uint64_t*>(p), __ATOMIC_RELAXED, kResScope);
 }
 
 // oa / ob <- the N values at a / b once none is kResEmpty (either source may be null: nothing to wait for). Each
@@ -143,17 +139,13 @@ __device__ __forceinline__ bool poll_vals(const double* src, double (&out)[N], u
   return poll_vals2<N>(src, out, nullptr, dummy, lim);
 }
 
-// v <- M v (P x P row-major M in LDS or global)
+// v <- M v (P x P row-major M in LDS or global): mat_vec_acc from zero
 template <class V, int P>
 __device__ __forceinline__ void mat_vec(const double* __restrict__ M, V (&v)[P]) {
   V r[P];
 #pragma unroll
-  for (int i = 0; i < P; ++i) {
-    V acc = zero_s(V{});
-#pragma unroll
-    for (int l = 0; l < P; ++l) acc = fma_s(M[i * P + l], v[l], acc);
-    r[i] = acc;
-  }
+  for (int i = 0; i < P; ++i) r[i] = zero_s(V{});
+  mat_vec_acc<V, P>(M, v, r);
 #pragma unroll
   for (int i = 0; i < P; ++i) v[i] = r[i];
 }
@@ -185,16 +177,7 @@ __device__ __forceinline__ void wg_scan(V (&v)[P], const double* __restrict__ pw
     V u[P];
 #pragma unroll
     for (int i = 0; i < P; ++i) u[i] = shfl_up_s(v[i], dl);
-    if (lane >= dl) {
-      const double* __restrict__ M = pw + s * PP;
-#pragma unroll
-      for (int i = 0; i < P; ++i) {
-        V acc = v[i];
-#pragma unroll
-        for (int l = 0; l < P; ++l) acc = fma_s(M[i * P + l], u[l], acc);
-        v[i] = acc;
-      }
-    }
+    if (lane >= dl) mat_vec_acc<V, P>(pw + s * PP, u, v);
   }
   lds_barrier();  // earlier readers of sc are done
   if (lane >= 64 - LS) {
@@ -273,27 +256,14 @@ __global__ __launch_bounds__(kResWG) void k_res_setup(Coeffs cf, double* __restr
   double* pwg = pw0 + 9 * PP;
   const int t = threadIdx.x;
   if (t < P) {
-    double am[P + 1];
-#pragma unroll
-    for (int i = 0; i <= P; ++i) am[i] = -coeff(cf.a, cf.K, i);
     double m[P];
-#pragma unroll
-    for (int i = 0; i < P; ++i) m[i] = i == t ? 1.0 : 0.0;
-    for (int k = 0; k < kChunk; ++k) {
-      double acc = 0.0;
-#pragma unroll
-      for (int i = 1; i <= P; ++i) acc = fma(am[i], m[i - 1], acc);
-#pragma unroll
-      for (int i = P - 1; i > 0; --i) m[i] = m[i - 1];
-      m[0] = acc;
-      gk[k * P + t] = acc;
-    }
+    chunk_transition_column<P, true>(cf, t, m, gk);
 #pragma unroll
     for (int i = 0; i < P; ++i) pw0[i * P + t] = m[i];
   }
   lds_barrier();
   for (int s = 1; s <= 8; ++s) sq_step<P>(pw0 + (s - 1) * PP, pw0 + (s - 1) * PP, pw0 + s * PP);
-  for (int e = t; e < PP; e += kResWG) pwg[e] = pw0[Shape<S>::LOGCPT * PP + e];
+  for (int e = t; e < PP; e += kResWG) pwg[e] = pw0[kLogCpt<S> * PP + e];
   lds_barrier();
   for (int s = 1; s < 8; ++s) sq_step<P>(pwg + (s - 1) * PP, pwg + (s - 1) * PP, pwg + s * PP);
   sq_step<P>(pwg + 7 * PP, pwg + 7 * PP, pwg + 8 * PP);  // M_SB = M_T^256
@@ -305,13 +275,6 @@ __global__ __launch_bounds__(kResWG) void k_res_setup(Coeffs cf, double* __restr
   }
 }
 
-#ifdef GSDR_IIR_RES_TIMING
-#define GSDR_RES_TS0() uint64_t ts_[12] = {}; ts_[0] = wall_clock64();
-#define GSDR_RES_TS(i) ts_[i] = wall_clock64();
-#else
-#define GSDR_RES_TS0()
-#define GSDR_RES_TS(i)
-#endif
 // waves a SIMD for the register budget: 4 fit P <= 4 without spills (LDS holds 4 tiles a CU); P = 8 needs
 // ~230-250 VGPRs, 2 waves
 template <class S, int P>
@@ -323,15 +286,14 @@ template <class S, int P, bool VEC>
 __global__ __launch_bounds__(kResWG) __attribute__((amdgpu_waves_per_eu(res_waves<S, P>()))) void k_iir_resident(Coeffs cf, const S* __restrict__ x, const S* __restrict__ xh,
                                                         const S* __restrict__ yh, uint64_t n, S* __restrict__ y,
                                                         ResArgs ra) {
-  using Sh = Shape<S>;
+  using L = Tile<S>;
   using A = typename Acc<S>::type;
-  constexpr int NC = Sh::NC, PP = P * P;
-  constexpr int SPV = 16 / sizeof(S);               // samples per 16-byte load
-  constexpr int NV = Sh::TS / SPV / kResWG;         // 16-byte loads a thread
+  constexpr int NC = L::NC, PP = P * P;
   // LDS: the tile (x, then y, for the whole kernel), the scans' scratch, M0^(2^s) (s <= 8), the
   // superblock-level tables, small vectors. (Holding the chunk in registers instead let the compiler convert
   // and scale all 32 samples ahead of the recursion: 210-256 VGPRs.)
-  __shared__ __attribute__((aligned(16))) float tile[Sh::kTileFloats];
+  __shared__ __attribute__((aligned(16))) float tile_f[L::kBytes / sizeof(float)];
+  S* tile = reinterpret_cast<S*>(tile_f);
   __shared__ __attribute__((aligned(16))) double scd[4 * NC * P];  // the scans' wave aggregates
   __shared__ __attribute__((aligned(16))) double bnd[4 * NC * P];  // each wave's last chunk prefixes
   __shared__ double tab[res_tab_doubles<P>()];  // k_res_setup's tables
@@ -341,7 +303,6 @@ __global__ __launch_bounds__(kResWG) __attribute__((amdgpu_waves_per_eu(res_wave
   __shared__ A sv[2][P];           // the tile's entry state, s0
   __shared__ S pre[P];             // x[base - 1 - i], i < P
   const int t = threadIdx.x;
-  GSDR_RES_TS0();
   const int comp = t % NC;
   const int lc = t / NC;  // chunk within the tile
   // the tile this workgroup filters: the next ticket (not blockIdx.x), so every tile it waits for belongs to a
@@ -350,22 +311,18 @@ __global__ __launch_bounds__(kResWG) __attribute__((amdgpu_waves_per_eu(res_wave
   if (t == 0) tile_sh = atomicAdd(ra.ticket, 1u);
   __syncthreads();
   const uint32_t tile_id = tile_sh;
-  const uint64_t base = (uint64_t)tile_id * Sh::TS;
-  const uint64_t ntiles = (n + Sh::TS - 1) / Sh::TS;
-  const uint32_t tlen = n - base < (uint64_t)Sh::TS ? (uint32_t)(n - base) : (uint32_t)Sh::TS;
-  const bool whole = VEC && tlen == (uint32_t)Sh::TS;
+  const uint64_t base = (uint64_t)tile_id * L::TS;
+  const uint64_t ntiles = (n + L::TS - 1) / L::TS;
+  const uint32_t tlen = n - base < (uint64_t)L::TS ? (uint32_t)(n - base) : (uint32_t)L::TS;
+  const bool whole = VEC && tlen == (uint32_t)L::TS;
 
   // 1. loads first (in flight while the M0 powers are built), then the entry state s0 and the P samples
   //    before the tile: every workgroup reads the caller's histories before publishing anything, so the last
   //    tile (which waits for every aggregate) rewrites them only after all reads
   // the tile's loads first, then the tables and the P samples before the tile and the entry state (raw until
   // the tile has arrived); the coefficients come as doubles from the setup kernel (scalar loads)
-  float4 v4[NV];
-  if (whole) {
-    const float4* __restrict__ src = reinterpret_cast<const float4*>(x + base);
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v4[k] = src[k * kResWG + t];
-  }
+  float4 v4[L::NV];
+  if (whole) load_tile<L>(x, base, t, v4);
   constexpr int NTAB = res_tab_doubles<P>(), NTR = (NTAB + kResWG - 1) / kResWG;
   double tv[NTR];
 #pragma unroll
@@ -379,29 +336,12 @@ __global__ __launch_bounds__(kResWG) __attribute__((amdgpu_waves_per_eu(res_wave
     b[i] = ra.tabs[NTAB + i];
     am[i] = ra.tabs[NTAB + P + 1 + i];
   }
-  S pre_v = zero_s(S{}), s0_v = zero_s(S{});
-  if (t < P) {
-    pre_v = x_at(x, xh, cf.K, (int64_t)base - 1 - t);
-    if (yh && t < cf.K - 1) s0_v = yh[t];
-  }
-  GSDR_RES_TS(1);
+  const S pre_v = load_pre<P>(x, xh, cf.K, base, t);
+  S s0_v = zero_s(S{});
+  if (t < P && yh && t < cf.K - 1) s0_v = yh[t];
 
-  // the tile into LDS (rows of 33 floats per component), then each lane's chunk row into registers
-  if (whole) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-      const int idx = (k * kResWG + t) * SPV;  // SPV consecutive samples, one chunk row
-      float* d = reinterpret_cast<float*>(reinterpret_cast<S*>(tile) + Sh::at(idx));
-      d[0] = v4[k].x;
-      d[1] = v4[k].y;
-      d[2] = v4[k].z;
-      d[3] = v4[k].w;
-    }
-  } else {
-    for (int idx = t; idx < (int)Sh::TS; idx += kResWG) {
-      reinterpret_cast<S*>(tile)[Sh::at(idx)] = idx < (int)tlen ? x[base + idx] : zero_s(S{});
-    }
-  }
+  // the tile into LDS (rows of 33 floats per component, zeros past the input's end), then the tables
+  stage_tile<L, true>(tile, whole, v4, x, base, tlen, t);
 #pragma unroll
   for (int r = 0; r < NTR; ++r) {
     const int e = r * kResWG + t;
@@ -412,78 +352,27 @@ __global__ __launch_bounds__(kResWG) __attribute__((amdgpu_waves_per_eu(res_wave
     sv[1][t] = to_acc(s0_v);
   }
   lds_barrier();
-  GSDR_RES_TS(2);
-  // this lane's chunk (component comp); not __restrict__: the rows are read through `tile` by other lanes and by
-  // the coalesced output loop, and restrict would let the compiler move those accesses across this lane's stores
-  float* row = tile + (size_t)lc * Sh::STRIDE * NC + comp;
-  double xd[P];  // component of x[n0 - 1 - i], read before any row is overwritten
-  {
-#pragma unroll
-    for (int i = 0; i < P; ++i) {
-      const int m = lc * kChunk - 1 - i;  // tile index of x[n0 - 1 - i]; < 0: before the tile
-      xd[i] = (double)reinterpret_cast<const float*>(m >= 0 ? reinterpret_cast<S*>(tile) + Sh::at(m) : pre + (-1 - m))[comp];
-    }
-  }
+  // this lane's chunk (component comp)
+  float* row = tile_f + (size_t)lc * L::STRIDE * NC + comp;
+  double xe[P];  // component of x[n0 - 1 - i], read before any row is overwritten; after the pass, the call's last inputs
+  prev_inputs<L, P>(tile, pre, lc, comp, xe);
   lds_barrier();
   const uint64_t n0 = base + (uint64_t)lc * kChunk;
   const uint32_t len = n0 >= n ? 0u : (n - n0 < (uint64_t)kChunk ? (uint32_t)(n - n0) : (uint32_t)kChunk);
-  // one chunk of the recursion from state ys (the feedback terms oldest first: one FMA on the critical path)
-  auto run_chunk = [&](double (&ys)[P], double (&xs)[P], bool write) {
-    auto step = [&](int k) {
-      const double xv = (double)row[k * NC];
-      double acc = b[0] * xv;
-#pragma unroll
-      for (int i = 1; i <= P; ++i) acc = fma(b[i], xs[i - 1], acc);
-#pragma unroll
-      for (int i = P; i >= 1; --i) acc = fma(am[i], ys[i - 1], acc);
-#pragma unroll
-      for (int i = P - 1; i > 0; --i) {
-        xs[i] = xs[i - 1];
-        ys[i] = ys[i - 1];
-      }
-      xs[0] = xv;
-      ys[0] = acc;
-      if (write) row[k * NC] = (float)acc;  // y replaces x in this chunk's row
-    };
-    if (len == (uint32_t)kChunk) {
-#pragma unroll
-      for (int k = 0; k < kChunk; ++k) step(k);
-    } else {
-      for (int k = 0; k < (int)len; ++k) step(k);
-    }
-  };
   // 1b. zero-state pass: the chunk's zero-state outputs replace its inputs in the row; the tail in registers
-  double tl[P], xe[P];
-  {
-    double ys[P];
-#pragma unroll
-    for (int i = 0; i < P; ++i) {
-      ys[i] = 0.0;
-      xe[i] = xd[i];
-    }
-    run_chunk(ys, xe, true);
-#pragma unroll
-    for (int i = 0; i < P; ++i) tl[i] = ys[i];
-  }
-  GSDR_RES_TS(3);
-  // 2. chunk prefixes across the workgroup (lanes of one component, NC apart); the last chunk's is the tile's
-  //    aggregate
   double pfx[P];
 #pragma unroll
-  for (int i = 0; i < P; ++i) pfx[i] = tl[i];
+  for (int i = 0; i < P; ++i) pfx[i] = 0.0;
+  run_chunk<P, NC, true>(row, len, b, am, xe, pfx);
+  // 2. chunk prefixes across the workgroup (lanes of one component, NC apart); the last chunk's is the tile's
+  //    aggregate
   wg_scan<double, P, NC>(pfx, pw0, scd);
   A* scA = reinterpret_cast<A*>(scd);
   const uint32_t sb = tile_id / kResSB, k_in = tile_id % kResSB;
-  if (lc == Sh::CPT - 1) {
+  if (lc == L::CPT - 1) {
 #pragma unroll
     for (int i = 0; i < P; ++i) st_co(ra.loc + ((size_t)tile_id * P + i) * NC + comp, pfx[i]);
   }
-#ifdef GSDR_IIR_RES_TIMING
-  GSDR_RES_TS(3);  // stores issued (the pass-1 mark moves here)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-#endif
-  GSDR_RES_TS(4);
 
   // 3. entry state of the tile: with L_j tile j's zero-entry aggregate, G_t superblock t's and k = k_in,
   //      S_tile = M_T^k S_sb + sum_{j<k} M_T^(k-1-j) L_j,   S_sb = M_SB^sb s0 + sum_{t<sb} M_SB^(sb-1-t) G_t.
@@ -520,7 +409,6 @@ __global__ __launch_bounds__(kResWG) __attribute__((amdgpu_waves_per_eu(res_wave
       mat_pow_vec<A, P>(pwg, k_in, qt);
     }
   };
-  GSDR_RES_TS(5);
   A tot[P];
   if (!last_in_sb) {
     {
@@ -528,7 +416,6 @@ __global__ __launch_bounds__(kResWG) __attribute__((amdgpu_waves_per_eu(res_wave
       double tu[NV2], tq[NV2];
       ok = poll_vals2<NV2>(u_mine ? ra.loc + (size_t)h * P * NC : nullptr, tu,
                            q_mine ? ra.sbagg + (size_t)t * P * NC : nullptr, tq, ra.max_polls) && ok;
-      GSDR_RES_TS(9);
 #pragma unroll
       for (int i = 0; i < P; ++i) {
 #pragma unroll
@@ -540,11 +427,9 @@ __global__ __launch_bounds__(kResWG) __attribute__((amdgpu_waves_per_eu(res_wave
     }
     q_term();
     if (u_mine) mat_pow_vec<A, P>(pwg, k_in - 1 - (uint32_t)t, ut);
-    GSDR_RES_TS(10);
 #pragma unroll
     for (int i = 0; i < P; ++i) ut[i] = add_s(ut[i], qt[i]);
     wg_sum<A, P>(ut, tot, scA);
-    GSDR_RES_TS(11);
   } else {
     // the superblock's aggregate first: G_sb = M_T (sum_{j<255} M_T^(254-j) L_j) + L_255 (the last thread
     // holds this tile's own L, the last chunk's prefix, for NC == 1; both components' lanes for NC == 2)
@@ -553,7 +438,7 @@ __global__ __launch_bounds__(kResWG) __attribute__((amdgpu_waves_per_eu(res_wave
     if (u_mine) mat_pow_vec<A, P>(pwg, k_in - 1 - (uint32_t)t, ut);
     A us[P];
     wg_sum<A, P>(ut, us, scA);
-    if (lc == Sh::CPT - 1 && sb + 1 < (ntiles + kResSB - 1) / kResSB) {
+    if (lc == L::CPT - 1 && sb + 1 < (ntiles + kResSB - 1) / kResSB) {
       double g[P];
 #pragma unroll
       for (int i = 0; i < P; ++i) g[i] = reinterpret_cast<const double*>(&us[i])[comp];
@@ -587,7 +472,6 @@ __global__ __launch_bounds__(kResWG) __attribute__((amdgpu_waves_per_eu(res_wave
 #pragma unroll
     for (int i = 0; i < P; ++i) pv[i] = bnd[((w - 1) * NC + comp) * P + i];
   }
-  GSDR_RES_TS(6);
   // 4. this chunk's start state M0^lc S_tile + prefix_(lc-1), the recursion again, y through LDS
   double st[P];
 #pragma unroll
@@ -618,7 +502,6 @@ __global__ __launch_bounds__(kResWG) __attribute__((amdgpu_waves_per_eu(res_wave
     }
   }
   lds_barrier();
-  GSDR_RES_TS(7);
   if (len > 0 && n0 + len == n && ok) {  // (a tile that gave up may not have waited for the readers)
     // the state after the call (outputs, then inputs, newest first) into the caller's history buffers: the
     // outputs as written (from the tile; before it, the tile's entry state)
@@ -627,33 +510,14 @@ __global__ __launch_bounds__(kResWG) __attribute__((amdgpu_waves_per_eu(res_wave
       if (i < ra.Pk) {
         const int m = (int)tlen - 1 - i;
         if (ra.yh_out) {
-          ra.yh_out[i * NC + comp] = m >= 0 ? reinterpret_cast<const float*>(reinterpret_cast<const S*>(tile) + Sh::at(m))[comp]
+          ra.yh_out[i * NC + comp] = m >= 0 ? reinterpret_cast<const float*>(tile + L::at(m))[comp]
                                             : (float)reinterpret_cast<const double*>(&sv[0][-1 - m])[comp];
         }
         if (ra.xh_out) ra.xh_out[i * NC + comp] = (float)xe[i];
       }
     }
   }
-  if (whole) {
-    float4* __restrict__ dst = reinterpret_cast<float4*>(y + base);
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-      const int idx = (k * kResWG + t) * SPV;
-      const float* d = reinterpret_cast<const float*>(reinterpret_cast<const S*>(tile) + Sh::at(idx));
-      dst[k * kResWG + t] = make_float4(d[0], d[1], d[2], d[3]);
-    }
-  } else {
-    for (int idx = t; idx < (int)tlen; idx += kResWG) y[base + idx] = reinterpret_cast<const S*>(tile)[Sh::at(idx)];
-  }
-#ifdef GSDR_IIR_RES_TIMING
-  __syncthreads();
-  ts_[8] = wall_clock64();
-  if (t == 0) {
-    uint64_t* o = reinterpret_cast<uint64_t*>(y + base);
-    for (int i = 0; i < 12; ++i) o[i] = ts_[i];
-    o[12] = __smid();
-  }
-#endif
+  store_tile<L>(tile, whole, y, base, tlen, t);
 }
 
 }  // namespace res

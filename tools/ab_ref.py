@@ -32,6 +32,9 @@ SIGS = {
     "gsdrQpsk256InitConstellation": [u32, f, i32, p],
     "gsdrIirFF": [p, p, sz, p, p, p, p, sz, i32, p],
     "gsdrIirCC": [p, p, sz, p, p, p, p, sz, i32, p],
+    # probes builds only (TREE_LIB=build/probes/libgsdr_probes.so against another build's probes library)
+    "gsdrxIirFFSinglePass": [p, p, sz, p, p, p, p, sz, u32, i32, p],
+    "gsdrxIirCCSinglePass": [p, p, sz, p, p, p, p, sz, u32, i32, p],
 }
 
 
@@ -45,7 +48,7 @@ def load(path):
 
 
 def main():
-    libs = [os.path.join(ROOT, "gsdr_amd", "libgsdr.so")] + sys.argv[1:]
+    libs = [os.path.join(ROOT, os.environ.get("TREE_LIB", os.path.join("gsdr_amd", "libgsdr.so")))] + sys.argv[1:]
     if os.environ.get("TREE_LAST") == "1":  # a second session with the order swapped: the working tree's library last
         libs = libs[1:] + libs[:1]
     L = [load(x) for x in libs]
@@ -71,6 +74,7 @@ def main():
 
     bb, aa = (torch.tensor(v, dtype=torch.float32, device=dev) for v in sps.butter(4, 0.1))
     bb8, aa8 = (torch.tensor(v, dtype=torch.float32, device=dev) for v in sps.butter(8, 0.2))
+    bb16, aa16 = (torch.tensor(v, dtype=torch.float32, device=dev) for v in sps.butter(16, 0.3))  # K > 9: unfused
     xis = [torch.rand(n5, device=dev, generator=g) for _ in range(4)]
     yis = [torch.empty_like(x) for x in xis]
     xics = [torch.rand(2 * n5, device=dev, generator=g).view(torch.complex64) for _ in range(4)]
@@ -112,7 +116,17 @@ def main():
                                                    yis[k % 4].data_ptr(), n5, 0, st),
         "gsdrIirCC9": lambda lib, k: lib.gsdrIirCC(bb8.data_ptr(), aa8.data_ptr(), 9, None, None, xics[k % 4].data_ptr(),
                                                    yics[k % 4].data_ptr(), n5, 0, st),
+        "gsdrIirFF17": lambda lib, k: lib.gsdrIirFF(bb16.data_ptr(), aa16.data_ptr(), 17, None, None, xis[k % 4].data_ptr(),
+                                                    yis[k % 4].data_ptr(), n5, 0, st),
+        "gsdrIirCC17": lambda lib, k: lib.gsdrIirCC(bb16.data_ptr(), aa16.data_ptr(), 17, None, None, xics[k % 4].data_ptr(),
+                                                    yics[k % 4].data_ptr(), n5, 0, st),
     }
+    # the single-pass IIR of the probes builds, orders 4 and 8 (poll bound 2^22, the measured setting)
+    for tag, bq, aq in (("5", bb, aa), ("9", bb8, aa8)):
+        cases["gsdrxIirFFSinglePass" + tag] = lambda lib, k, bq=bq, aq=aq: lib.gsdrxIirFFSinglePass(
+            bq.data_ptr(), aq.data_ptr(), bq.numel(), None, None, xis[k % 4].data_ptr(), yis[k % 4].data_ptr(), n5, 1 << 22, 0, st)
+        cases["gsdrxIirCCSinglePass" + tag] = lambda lib, k, bq=bq, aq=aq: lib.gsdrxIirCCSinglePass(
+            bq.data_ptr(), aq.data_ptr(), bq.numel(), None, None, xics[k % 4].data_ptr(), yics[k % 4].data_ptr(), n5, 1 << 22, 0, st)
     only = os.environ.get("CASES")
     res = {}
     for r in range(ROUNDS):
@@ -122,6 +136,8 @@ def main():
             for li in [(r + x) % len(L) for x in range(len(L))]:  # the order rotates round by round
                 lib = L[li]
                 if name == "config5_fused" and not hasattr(lib, "gsdrxQpsk256ModulateAwgnDemodulate"):
+                    continue
+                if "SinglePass" in name and not hasattr(lib, name[:-1]):
                     continue
                 for k in range(5 + SETTLE):  # SETTLE: sustained-clock timing like bench.py's (default: short bursts)
                     assert fn(lib, k) == 0
