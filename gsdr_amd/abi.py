@@ -105,6 +105,12 @@ SIGNATURES = {
     "gsdrxStreamDestroy": (_err, [_p]),
     "gsdrxStreamPlan": (None, [_u32, _sz, ctypes.c_uint64, ctypes.c_uint64, _sz, ctypes.POINTER(ctypes.c_uint64)]),
     "gsdrxAmDemodInt8": (_err, [_f, _f, _f, _u32, _sz, _p, _sz, _p, _p, _sz, _i32, _p]),
+    # resampler.h
+    "gsdrxResamplerCreate": (_err, [ctypes.POINTER(_p), _int, _u32, _u32, _u32, _p, _sz, _i32]),
+    "gsdrxResamplerOutputsFor": (_sz, [_p, _sz]),
+    "gsdrxResamplerProcess": (_err, [_p, _p, _sz, _p, _sz, ctypes.POINTER(_sz), _p]),
+    "gsdrxResamplerDestroy": (_err, [_p]),
+    "gsdrxResamplerPlan": (None, [_u32, _u32, _u64, _u32, _u64, _u64, _u64, ctypes.POINTER(_u64)]),
 }
 
 

@@ -4,12 +4,22 @@
 // only the taps that meet a real sample are multiplied. Every output component is one ascending-p fmaf chain from
 // +0 in both kernels, so the bits depend on neither the route, the tile size nor where a stream is cut into calls.
 // The launch plan is resample_plan.hpp.
+//
+// gsdrxResampler (include/gsdr/resampler.h) is the stream form: host bookkeeping (resample_stream_plan.hpp) around
+// the same kernels. On the tile route a call is one launch of k_resample_tile<S, true>, which stages a tile from
+// the kept history and then from the caller's chunk, with one appended workgroup that copies the next history.
 #include <hip/hip_runtime.h>
+
+#include <new>
+#include <type_traits>
+#include <utility>
 
 #include "gsdr/fir.h"
 #include "gsdr/gsdr_ext.h"
+#include "gsdr/resampler.h"
 #include "launch.hpp"
 #include "resample_plan.hpp"
+#include "resample_stream_plan.hpp"
 
 namespace gsdr {
 namespace resample {
@@ -92,14 +102,62 @@ __device__ __forceinline__ uint32_t div_l(uint32_t u, uint32_t L, uint32_t magic
   return e;
 }
 
+// The small device-to-device moves of one streaming call (next history; on the seam plan also history + chunk head
+// into the seam buffer), in 4-byte words: a sample is one or two of them. Segments never overlap (they write the
+// spare history or the seam buffer and read the history in use or the chunk).
+struct Moves {
+  static constexpr int kMax = 4;
+  struct Seg {
+    float* dst;
+    const float* src;
+    uint64_t words;
+  } seg[kMax];
+  int n = 0;
+  void add(void* dst, const void* src, uint64_t words) {
+    if (words) seg[n++] = Seg{static_cast<float*>(dst), static_cast<const float*>(src), words};
+  }
+};
+
+__device__ __forceinline__ void move_words(const Moves& mv, uint64_t first, uint64_t stride) {
+  for (int i = 0; i < mv.n; ++i) {
+    for (uint64_t k = first; k < mv.seg[i].words; k += stride) mv.seg[i].dst[k] = mv.seg[i].src[k];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_resample_moves(const Moves mv) {
+  move_words(mv, threadIdx.x + (uint64_t)blockIdx.x * blockDim.x, (uint64_t)gridDim.x * blockDim.x);
+}
+
+// What a streaming launch of the tiled kernel adds. The call's input is the virtual array history ++ chunk: Params::in
+// is placed so that in[n] is the chunk's sample for n >= split, and in[n] for hist_first <= n < split is
+// hist[n - hist_first] (hist_first = 0 or 1: index 0 is never read when the call's phase is not 0).
+struct StreamArgs {
+  const void* hist;
+  uint64_t split;
+  uint32_t hist_first;
+  uint32_t tiles;  // workgroups that compute; workgroup `tiles` copies the next history
+  Moves next;
+};
+struct NoStream {};
+
 // One workgroup a tile of KT = kR * blockDim.x consecutive outputs: the tile's input span and all T taps are staged
 // into LDS, then thread `tid` computes outputs tid, tid + WG, ... of the tile (coalesced stores). Lane j's tap
 // reads taps[i0(j) + p L]: the taps' natural order is the [p][phase] layout. The first T / L steps meet a tap for
 // every output; step T / L only for outputs with i0 + (T / L) L < T, and no product past tap T - 1 is formed.
-template <class S>
-__global__ __launch_bounds__(kMaxWG) void k_resample_tile(const Params p, const TileArgs a) {
+// STREAM (gsdrxResamplerProcess): the part of a tile's span in front of the chunk, fewer than ceil(T / L) samples and
+// met only by the first tiles, comes from the history element by element, placed so that the chunk part keeps the
+// granule staging; the LDS image holds the values of the one-shot call, so the outputs' bits are that call's.
+template <class S, bool STREAM>
+__global__ __launch_bounds__(kMaxWG) void k_resample_tile(const Params p, const TileArgs a,
+                                                          const std::conditional_t<STREAM, StreamArgs, NoStream> sa) {
   extern __shared__ f32x4 lds16[];
   const uint32_t tid = threadIdx.x, wg = blockDim.x, KT = kR * wg;
+  if constexpr (STREAM) {
+    if (blockIdx.x == sa.tiles) {
+      move_words(sa.next, tid, wg);
+      return;
+    }
+  }
   const uint32_t L = p.L, M = p.M, T = (uint32_t)p.T;
   const uint64_t m0 = (uint64_t)blockIdx.x * KT;
   const uint32_t kt = p.N - m0 < KT ? (uint32_t)(p.N - m0) : KT;  // outputs of this tile (>= 1)
@@ -130,10 +188,28 @@ __global__ __launch_bounds__(kMaxWG) void k_resample_tile(const Params p, const 
   constexpr uint32_t G = 16 / sizeof(S);
   S* xs = reinterpret_cast<S*>(lds16);
   float* ts = reinterpret_cast<float*>(lds16 + ((size_t)(a.span + G - 1) * sizeof(S) + 15) / 16);
-  const S* src = static_cast<const S*>(p.in) + n_first;
-  const uint32_t xoff = granule_offset(src), toff = granule_offset(p.taps);
+  const uint32_t toff = granule_offset(p.taps);
+  uint32_t xoff;
   // the samples stream through once (non-temporal); every workgroup reads the taps again (cached)
-  if (count > 0) stage<true>(xs, src, xoff, count, tid, wg);
+  if constexpr (STREAM) {
+    const uint64_t ahead = sa.split > n_first ? sa.split - n_first : 0;  // samples in front of the chunk
+    const uint32_t hc = count < ahead ? count : (uint32_t)ahead;
+    const S* src = static_cast<const S*>(p.in) + (n_first + hc);
+    const uint32_t coff = granule_offset(src);
+    xoff = (coff - hc) % G;  // the chunk part lands at its own granule offset, coff = (xoff + hc) mod G
+    // a thread's (first) history sample is loaded ahead of its chunk granules and stored behind them, so that the
+    // first tile pays one trip to memory for both and not one after the other
+    const S* hs = static_cast<const S*>(sa.hist) + (n_first - sa.hist_first);
+    S mine = S();
+    if (tid < hc) mine = hs[tid];
+    if (count > hc) stage<true>(xs + (xoff + hc - coff), src, coff, count - hc, tid, wg);
+    if (tid < hc) xs[xoff + tid] = mine;
+    for (uint32_t e = tid + wg; e < hc; e += wg) xs[xoff + e] = hs[e];
+  } else {
+    const S* src = static_cast<const S*>(p.in) + n_first;
+    xoff = granule_offset(src);
+    if (count > 0) stage<true>(xs, src, xoff, count, tid, wg);
+  }
   stage<false>(ts, p.taps, toff, T, tid, wg);
   __syncthreads();
 
@@ -215,8 +291,9 @@ __global__ __launch_bounds__(kGenericWG) void k_resample_generic(const Params p)
   static_cast<V*>(p.out)[m] = acc;
 }
 
+// sa: the streaming operands of a tile-route launch (one more workgroup), null for a one-shot call
 template <class S>
-static hipError_t launch(const Params& p, const Plan& pl, hipStream_t stream) {
+static hipError_t launch(const Params& p, const Plan& pl, hipStream_t stream, const StreamArgs* sa = nullptr) {
   if (pl.route == kRouteTile) {
     TileArgs a;
     a.span = pl.span;
@@ -228,7 +305,13 @@ static hipError_t launch(const Params& p, const Plan& pl, hipStream_t stream) {
     a.tile_r = tile % p.L;
     a.step_q = step / p.L;
     a.step_r = step % p.L;
-    k_resample_tile<S><<<dim3((uint32_t)pl.blocks), dim3(pl.wg), pl.lds_bytes, stream>>>(p, a);
+    if (sa != nullptr) {
+      StreamArgs st = *sa;
+      st.tiles = (uint32_t)pl.blocks;
+      k_resample_tile<S, true><<<dim3((uint32_t)pl.blocks + 1), dim3(pl.wg), pl.lds_bytes, stream>>>(p, a, st);
+    } else {
+      k_resample_tile<S, false><<<dim3((uint32_t)pl.blocks), dim3(pl.wg), pl.lds_bytes, stream>>>(p, a, NoStream{});
+    }
   } else {
     k_resample_generic<S><<<dim3((uint32_t)pl.blocks), dim3(pl.wg), 0, stream>>>(p);
   }
@@ -275,8 +358,215 @@ static hipError_t entry(uint32_t L, uint32_t M, uint32_t phase, const float* tap
   return launch<S>(p, pl, stream);
 }
 
+static hipError_t moves(const Moves& mv, hipStream_t stream) {
+  if (mv.n == 0) return hipSuccess;
+  uint64_t most = 0;
+  for (int i = 0; i < mv.n; ++i) most = mv.seg[i].words > most ? mv.seg[i].words : most;
+  const uint32_t blocks = (uint32_t)(most < 64 * 1024 ? ceil_div64(most, 1024) : 64);
+  k_resample_moves<<<blocks, 256, 0, stream>>>(mv);
+  return launch_status();
+}
+
 }  // namespace resample
 }  // namespace gsdr
+
+struct gsdrxResampler_t {
+  uint32_t L = 1, M = 1, phase0 = 0;
+  const float* taps = nullptr;
+  size_t T = 0;
+  int32_t device = 0;
+  size_t sb = 4;       // bytes per sample
+  bool tiled = false;  // one launch a call (k_resample_tile<S, true>); else the seam plan through the one-shot calls
+  uint64_t consumed = 0;
+  uint64_t next_out = 0;
+  char* hist = nullptr;   // x[ceil(s / L) .. consumed), s = phase0 + next_out M (empty when that lies beyond)
+  char* spare = nullptr;  // the other history buffer (ping-pong)
+  char* seam = nullptr;   // seam plan: history + chunk head for the outputs that start in the history
+};
+
+namespace gsdr {
+namespace resample {
+
+// p + n samples of sb bytes, n possibly negative: the origin of a virtual input, formed without stepping a pointer
+// outside its buffer (only addresses inside the chunk are ever read through it)
+static const char* offset_by(const char* p, int64_t n, size_t sb) {
+  return reinterpret_cast<const char*>(reinterpret_cast<uintptr_t>(p) + (uintptr_t)n * sb);
+}
+
+template <class S>
+static hipError_t process(gsdrxResampler_t& r, const StreamPlan& sp, const char* chunk, uint64_t len, S* out,
+                          hipStream_t stream) {
+  const uint64_t Sx = r.consumed, words = sizeof(S) / 4;
+  uint64_t s = 0;
+  (void)stream_stuffed(r.phase0, r.M, r.T, r.next_out, &s);  // (the plan checked it)
+  // the next history: the tail of the chunk, or the tail of the old history and the whole chunk
+  Moves next;
+  if (sp.hist_after) {
+    uint64_t kept = 0;
+    if (sp.first_after < Sx) {
+      kept = Sx - sp.first_after;
+      next.add(r.spare, r.hist + (sp.first_after - sp.first) * sizeof(S), kept * words);
+    }
+    const uint64_t c0 = sp.first_after > Sx ? sp.first_after - Sx : 0;
+    next.add(r.spare + kept * sizeof(S), chunk + c0 * sizeof(S), (len - c0) * words);
+  }
+  if (sp.outputs == 0) return moves(next, stream);
+  if (r.tiled) {
+    // ONE launch: the one-shot call at output next_out (origin x[s / L], phase s mod L) over history ++ chunk
+    const uint64_t origin = s / r.L;
+    uint64_t extent = 0;
+    Plan pl{};
+    if (!stuffed_extent(s % r.L, r.M, r.T, sp.outputs, &extent) || !plan(r.L, r.M, r.T, sizeof(S), sp.outputs, &pl)) {
+      return hipErrorInvalidValue;
+    }
+    Params p{};
+    p.in = offset_by(chunk, (int64_t)(origin - Sx), sizeof(S));
+    p.taps = r.taps;
+    p.out = out;
+    p.N = sp.outputs;
+    p.need = inputs_for(r.L, extent);
+    p.phase = s % r.L;
+    p.T = r.T;
+    p.L = r.L;
+    p.M = r.M;
+    StreamArgs sa{};
+    sa.hist = r.hist;
+    sa.split = Sx > origin ? Sx - origin : 0;
+    sa.hist_first = (uint32_t)(sp.first - origin);  // 0 or 1
+    sa.next = next;
+    return launch<S>(p, pl, stream, &sa);
+  }
+  // the seam plan: history + chunk head gathered into the seam buffer (with the next history, one launch), then
+  // the outputs that start in the history and the remaining ones as two one-shot calls
+  Moves mv = next;
+  const uint64_t origin = s / r.L, lead = sp.first - origin;  // the seam buffer starts at x[origin]
+  if (sp.seam) {
+    uint64_t s_last = 0;
+    (void)stream_stuffed(r.phase0, r.M, r.T, r.next_out + sp.seam - 1, &s_last);
+    const uint64_t head = (s_last + r.T - 1) / r.L + 1 - Sx;  // chunk samples the last seam output reads
+    mv.add(r.seam + lead * sizeof(S), r.hist, sp.hist * words);
+    mv.add(r.seam + (lead + sp.hist) * sizeof(S), chunk, head * words);
+  }
+  hipError_t e = moves(mv, stream);
+  if (e == hipSuccess && sp.seam) {
+    e = entry<S>(r.L, r.M, (uint32_t)(s % r.L), r.taps, r.T, reinterpret_cast<const S*>(r.seam), out, sp.seam,
+                 r.device, stream);
+  }
+  if (e == hipSuccess && sp.outputs > sp.seam) {
+    uint64_t s_mid = 0;
+    (void)stream_stuffed(r.phase0, r.M, r.T, r.next_out + sp.seam, &s_mid);
+    const char* in = offset_by(chunk, (int64_t)(s_mid / r.L - Sx), sizeof(S));
+    e = entry<S>(r.L, r.M, (uint32_t)(s_mid % r.L), r.taps, r.T, reinterpret_cast<const S*>(in), out + sp.seam,
+                 sp.outputs - sp.seam, r.device, stream);
+  }
+  return e;
+}
+
+}  // namespace resample
+}  // namespace gsdr
+
+GSDR_C_LINKAGE hipError_t gsdrxResamplerCreate(gsdrxResampler* resampler, int sampleType, uint32_t interpolation,
+                                               uint32_t decimation, uint32_t phase, const float* taps, size_t numTaps,
+                                               int32_t cudaDevice) GSDR_NO_EXCEPT {
+  if (resampler == nullptr) return hipErrorInvalidValue;
+  *resampler = nullptr;
+  if (sampleType != GSDRX_RESAMPLER_F32 && sampleType != GSDRX_RESAMPLER_CF32) return hipErrorInvalidValue;
+  if (interpolation == 0 || decimation == 0 || phase >= interpolation) return hipErrorInvalidValue;
+  if (taps == nullptr || numTaps == 0) return hipErrorInvalidValue;
+  gsdrxResampler r = new (std::nothrow) gsdrxResampler_t;
+  if (r == nullptr) return hipErrorOutOfMemory;
+  r->L = interpolation;
+  r->M = decimation;
+  r->phase0 = phase;
+  r->taps = taps;
+  r->T = numTaps;
+  r->device = cudaDevice;
+  r->sb = sampleType == GSDRX_RESAMPLER_CF32 ? 8 : 4;
+  if (interpolation > 1) {  // (interpolation == 1 is gsdrFirFF / FC: the seam plan)
+    gsdr::resample::Plan pl{};
+    gsdr::resample::route_of(interpolation, decimation, numTaps, r->sb, &pl);
+    r->tiled = pl.route == gsdr::resample::kRouteTile;
+  }
+  gsdr::DeviceScope scope(cudaDevice);
+  hipError_t e = scope.status();
+  const size_t most = (size_t)gsdr::resample::ceil_div64(numTaps, interpolation);  // samples an output reads at most
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&r->hist), most * r->sb);  // history < most samples
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&r->spare), most * r->sb);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&r->seam), 2 * most * r->sb);  // 1 + 2 (most - 1)
+  if (e != hipSuccess) {
+    (void)gsdrxResamplerDestroy(r);
+    return e;
+  }
+  *resampler = r;
+  return hipSuccess;
+}
+
+GSDR_C_LINKAGE size_t gsdrxResamplerOutputsFor(gsdrxResampler r, size_t numInputSamples) GSDR_NO_EXCEPT {
+  gsdr::resample::StreamPlan sp;
+  if (r == nullptr) return 0;
+  if (!gsdr::resample::stream_plan(r->L, r->M, r->T, r->phase0, r->consumed, r->next_out, numInputSamples, &sp)) return 0;
+  return (size_t)sp.outputs;
+}
+
+GSDR_C_LINKAGE hipError_t gsdrxResamplerProcess(gsdrxResampler r, const void* input, size_t numInputSamples,
+                                                void* output, size_t outputCapacity, size_t* numOutputsWritten,
+                                                hipStream_t cudaStream) GSDR_NO_EXCEPT {
+  if (numOutputsWritten) *numOutputsWritten = 0;
+  if (r == nullptr) return hipErrorInvalidValue;
+  if (numInputSamples == 0) return hipSuccess;
+  if (input == nullptr) return hipErrorInvalidValue;
+  gsdr::resample::StreamPlan sp;
+  if (!gsdr::resample::stream_plan(r->L, r->M, r->T, r->phase0, r->consumed, r->next_out, numInputSamples, &sp)) {
+    return hipErrorInvalidValue;
+  }
+  if (sp.outputs > outputCapacity || (sp.outputs && output == nullptr)) return hipErrorInvalidValue;
+  gsdr::DeviceScope scope(r->device);
+  if (scope.status() != hipSuccess) return scope.status();
+  const char* chunk = static_cast<const char*>(input);
+  const hipError_t e =
+      r->sb == 8 ? gsdr::resample::process<float2>(*r, sp, chunk, numInputSamples, static_cast<float2*>(output), cudaStream)
+                 : gsdr::resample::process<float>(*r, sp, chunk, numInputSamples, static_cast<float*>(output), cudaStream);
+  if (e != hipSuccess) return e;
+  if (sp.hist_after) std::swap(r->hist, r->spare);
+  r->consumed += numInputSamples;
+  r->next_out += sp.outputs;
+  if (numOutputsWritten) *numOutputsWritten = (size_t)sp.outputs;
+  return hipSuccess;
+}
+
+GSDR_C_LINKAGE hipError_t gsdrxResamplerDestroy(gsdrxResampler r) GSDR_NO_EXCEPT {
+  if (r == nullptr) return hipSuccess;
+  hipError_t e = hipSuccess;
+  {
+    gsdr::DeviceScope scope(r->device);
+    if (scope.status() == hipSuccess) {
+      for (char* b : {r->hist, r->spare, r->seam}) {
+        if (b) {
+          const hipError_t f = hipFree(b);
+          if (e == hipSuccess) e = f;
+        }
+      }
+    } else {
+      e = scope.status();
+    }
+  }
+  delete r;
+  return e;
+}
+
+GSDR_C_LINKAGE void gsdrxResamplerPlan(uint32_t interpolation, uint32_t decimation, uint64_t numTaps, uint32_t phase,
+                                       uint64_t consumed, uint64_t nextOutput, uint64_t chunk,
+                                       uint64_t plan[6]) GSDR_NO_EXCEPT {
+  if (plan == nullptr) return;
+  gsdr::resample::StreamPlan sp;
+  (void)gsdr::resample::stream_plan(interpolation, decimation, numTaps, phase, consumed, nextOutput, chunk, &sp);
+  plan[0] = sp.outputs;  // (all zero when refused)
+  plan[1] = sp.seam;
+  plan[2] = sp.hist;
+  plan[3] = sp.skip;
+  plan[4] = sp.hist_after;
+  plan[5] = sp.skip_after;
+}
 
 GSDR_C_LINKAGE hipError_t gsdrxResampleFF(uint32_t interpolation, uint32_t decimation, uint32_t phase,
                                           const float* taps, size_t numTaps, const float* input, float* output,

@@ -1,0 +1,80 @@
+// gsdr-mi355x: what one gsdrxResamplerProcess call (include/gsdr/resampler.h, resample.hip) does, as a pure
+// function of the filter's shape and the stream's position: no HIP, so it can be compiled and checked on the host
+// alone (gsdrxResamplerPlan exposes it).
+//
+// L = interpolation, M = decimation, T = taps >= 1, q = phase0 < L. Output m's window starts at s(m) = q + m M of
+// the zero-stuffed stream; it reads the samples [first(m), need(m)) of the stream,
+//     first(m) = ceil(s(m) / L),   need(m) = floor((s(m) + T - 1) / L) + 1   (gsdrxResampleInputsFor of m + 1 outputs),
+// none when the window holds no tap (first = need), and is written by the first call after which need(m) samples
+// have arrived. Both are non-decreasing in m, and need(m) - first(m) <= ceil(T / L).
+//
+// Between calls the object keeps x[first(m) .. consumed) for m = the next output. That output has not been written,
+// so need(m) > consumed, hence consumed - first(m) < need(m) - first(m) <= ceil(T / L): the history holds at most
+// ceil(T / L) - 1 samples. When M / L is large first(m) may lie beyond consumed: the history is empty and
+// first(m) - consumed samples of the coming chunks are skipped.
+#pragma once
+
+#include <stdint.h>
+
+namespace gsdr {
+namespace resample {
+
+struct StreamPlan {
+  uint64_t outputs;     // outputs this call writes
+  uint64_t seam;        // the first `seam` of them start in the history (first(m) < consumed)
+  uint64_t hist;        // history samples in use before the call
+  uint64_t skip;        // samples at the head of the chunk that no output reads: min(first(m) - consumed, chunk)
+  uint64_t hist_after;  // history samples after the call
+  uint64_t skip_after;  // samples of later chunks still to skip after the call
+  // for the launches: first(m) of the next output before and after the call
+  uint64_t first, first_after;
+};
+
+typedef unsigned __int128 stream_u128;
+
+// s(m) = q + m M when s(m) + T stays within 63 bits
+inline bool stream_stuffed(uint64_t q, uint64_t M, uint64_t T, uint64_t m, uint64_t* s) {
+  const stream_u128 v = (stream_u128)m * M + q;
+  if (((v + T) >> 63) != 0) return false;
+  *s = (uint64_t)v;
+  return true;
+}
+
+// Outputs whose samples all lie in x[0, S): the m with s(m) + T <= S L, from 0.
+inline uint64_t stream_outputs_through(uint64_t L, uint64_t M, uint64_t T, uint64_t q, uint64_t S) {
+  const stream_u128 have = (stream_u128)S * L, least = (stream_u128)T + q;
+  if (have < least) return 0;
+  const stream_u128 n = (have - least) / M + 1;
+  return (n >> 64) != 0 ? ~0ull : (uint64_t)n;
+}
+
+// The call that appends `chunk` samples to a stream of which `S` have arrived and `m` outputs are written. False:
+// refused (a bad shape, or the zero-stuffed index s + T of an output of this call or of the next one leaves 63 bits).
+inline bool stream_plan(uint64_t L, uint64_t M, uint64_t T, uint64_t q, uint64_t S, uint64_t m, uint64_t chunk,
+                        StreamPlan* p) {
+  *p = StreamPlan{};
+  uint64_t S1 = 0, s = 0, s_end = 0;
+  if (L == 0 || M == 0 || T == 0 || q >= L || __builtin_add_overflow(S, chunk, &S1)) return false;
+  uint64_t m_end = stream_outputs_through(L, M, T, q, S1);
+  if (m_end < m) m_end = m;
+  if (!stream_stuffed(q, M, T, m, &s) || !stream_stuffed(q, M, T, m_end, &s_end)) return false;
+  p->outputs = m_end - m;
+  p->first = s / L + (s % L != 0);
+  p->first_after = s_end / L + (s_end % L != 0);
+  // first(m') < S  <=>  s(m') <= (S - 1) L
+  uint64_t m_mid = m;
+  if (S > 0 && (stream_u128)(S - 1) * L >= q) {
+    const stream_u128 n = ((stream_u128)(S - 1) * L - q) / M + 1;
+    m_mid = n > m_end ? m_end : (uint64_t)n;
+    if (m_mid < m) m_mid = m;
+  }
+  p->seam = m_mid - m;
+  p->hist = S > p->first ? S - p->first : 0;
+  p->skip = p->first > S ? (p->first - S < chunk ? p->first - S : chunk) : 0;
+  p->hist_after = S1 > p->first_after ? S1 - p->first_after : 0;
+  p->skip_after = p->first_after > S1 ? p->first_after - S1 : 0;
+  return true;
+}
+
+}  // namespace resample
+}  // namespace gsdr

@@ -11,6 +11,9 @@ Concatenated over the calls, the outputs equal one gsdrFirFC / gsdrFmDemod / gsd
 A list of channel frequencies (and, for FM, of deviations) makes a multi-channel stream
 (gsdrxStreamCreateMulti): process() then returns a (channels, outputs) tensor whose row c is the
 single-channel stream of channel c, bit for bit.
+
+Resampler is the same for the rational resampler (include/gsdr/resampler.h): chunks in, the outputs of one
+ops.resample call over the concatenated input out, bit for bit.
 """
 from __future__ import annotations
 
@@ -95,6 +98,72 @@ class Stream:
             self.close()
         except Exception:
             pass
+
+
+class Resampler:
+    """gsdrxResampler (include/gsdr/resampler.h): the stream form of ops.resample.
+
+        r = Resampler(taps, interpolation=24, decimation=125)
+        for chunk in chunks:            # float32 (or complex64) device tensors of any length
+            audio = r.process(chunk)    # every output that became computable, in order
+
+    Concatenated over the calls, the outputs equal one gsdrxResampleFF / FC call over the concatenated input, bit
+    for bit."""
+
+    def __init__(self, taps: torch.Tensor, interpolation: int, decimation: int, phase: int = 0,
+                 complex_samples: bool = False):
+        if taps.dtype != torch.float32 or taps.device.type != "cuda" or not taps.is_contiguous():
+            raise TypeError("taps must be a contiguous float32 device tensor")
+        L, M, q = int(interpolation), int(decimation), int(phase)
+        if not (1 <= L < 1 << 32 and 1 <= M < 1 << 32 and 0 <= q < L):
+            raise ValueError(f"need interpolation, decimation in [1, 2^32) and phase in [0, interpolation); got {L}, {M}, {q}")
+        self.taps = taps  # keep taps alive: the object reads them
+        self.device = taps.device
+        self.dtype = torch.complex64 if complex_samples else torch.float32
+        self._h = ctypes.c_void_p()
+        check("gsdrxResamplerCreate", lib.gsdrxResamplerCreate(
+            ctypes.byref(self._h), 1 if complex_samples else 0, L, M, q, taps.data_ptr(), taps.numel(),
+            self.device.index))
+
+    def outputs_for(self, num_samples: int) -> int:
+        return lib.gsdrxResamplerOutputsFor(self._h, num_samples)
+
+    def process(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        if x.dtype != self.dtype or not x.is_contiguous() or x.device != self.device:
+            raise TypeError(f"input must be a contiguous {self.dtype} tensor on {self.device}")
+        n_in = x.numel()
+        n_out = self.outputs_for(n_in)
+        if out is None:
+            out = torch.empty(n_out, dtype=self.dtype, device=self.device)
+        if out.dtype != self.dtype or out.numel() < n_out or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"output must be a contiguous tensor of at least {n_out} {self.dtype} values on {self.device}")
+        written = ctypes.c_size_t(0)
+        check("gsdrxResamplerProcess", lib.gsdrxResamplerProcess(self._h, x.data_ptr() if n_in else None, n_in,
+                                                                 out.data_ptr() if n_out else None, out.numel(),
+                                                                 ctypes.byref(written), stream_of(x)))
+        if written.value != n_out:
+            raise GsdrError("gsdrxResamplerProcess", -1)
+        return out.view(-1)[:n_out]
+
+    def close(self):
+        if self._h:
+            check("gsdrxResamplerDestroy", lib.gsdrxResamplerDestroy(self._h))
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def resampler_plan(interpolation: int, decimation: int, num_taps: int, phase: int, consumed: int, next_output: int,
+                   chunk: int):
+    """gsdrxResamplerPlan: (outputs, seam outputs, history before, chunk samples skipped, history after, samples
+    still to skip)."""
+    out = (ctypes.c_uint64 * 6)()
+    lib.gsdrxResamplerPlan(interpolation, decimation, num_taps, phase, consumed, next_output, chunk, out)
+    return tuple(int(v) for v in out)
 
 
 def plan(decimation: int, window: int, consumed: int, next_output: int, chunk: int):
