@@ -5,21 +5,20 @@
 // +0 in both kernels, so the bits depend on neither the route, the tile size nor where a stream is cut into calls.
 // The launch plan is resample_plan.hpp.
 //
-// gsdrxResampler (include/gsdr/resampler.h) is the stream form: host bookkeeping (resample_stream_plan.hpp) around
-// the same kernels. On the tile route a call is one launch of k_resample_tile<S, true>, which stages a tile from
+// gsdrxResampler (include/gsdr/resampler.h) is the stream form: the host bookkeeping of every stream
+// (stream_plan.hpp, stream_buffers.hpp) around the same kernels. On the tile route a call is one launch of k_resample_tile<S, true>, which stages a tile from
 // the kept history and then from the caller's chunk, with one appended workgroup that copies the next history.
 #include <hip/hip_runtime.h>
 
 #include <new>
 #include <type_traits>
-#include <utility>
 
 #include "gsdr/fir.h"
 #include "gsdr/gsdr_ext.h"
 #include "gsdr/resampler.h"
 #include "launch.hpp"
 #include "resample_plan.hpp"
-#include "resample_stream_plan.hpp"
+#include "stream_buffers.hpp"
 
 namespace gsdr {
 namespace resample {
@@ -102,9 +101,8 @@ __device__ __forceinline__ uint32_t div_l(uint32_t u, uint32_t L, uint32_t magic
   return e;
 }
 
-// The small device-to-device moves of one streaming call (next history; on the seam plan also history + chunk head
-// into the seam buffer), in 4-byte words: a sample is one or two of them. Segments never overlap (they write the
-// spare history or the seam buffer and read the history in use or the chunk).
+// The next-history moves of one streaming call (stream_next_history, stream_plan.hpp) as the tiled kernel's appended
+// workgroup takes them: in 4-byte words, a sample is one or two of them.
 struct Moves {
   static constexpr int kMax = 4;
   struct Seg {
@@ -122,10 +120,6 @@ __device__ __forceinline__ void move_words(const Moves& mv, uint64_t first, uint
   for (int i = 0; i < mv.n; ++i) {
     for (uint64_t k = first; k < mv.seg[i].words; k += stride) mv.seg[i].dst[k] = mv.seg[i].src[k];
   }
-}
-
-__global__ __launch_bounds__(256) void k_resample_moves(const Moves mv) {
-  move_words(mv, threadIdx.x + (uint64_t)blockIdx.x * blockDim.x, (uint64_t)gridDim.x * blockDim.x);
 }
 
 // What a streaming launch of the tiled kernel adds. The call's input is the virtual array history ++ chunk: Params::in
@@ -358,15 +352,6 @@ static hipError_t entry(uint32_t L, uint32_t M, uint32_t phase, const float* tap
   return launch<S>(p, pl, stream);
 }
 
-static hipError_t moves(const Moves& mv, hipStream_t stream) {
-  if (mv.n == 0) return hipSuccess;
-  uint64_t most = 0;
-  for (int i = 0; i < mv.n; ++i) most = mv.seg[i].words > most ? mv.seg[i].words : most;
-  const uint32_t blocks = (uint32_t)(most < 64 * 1024 ? ceil_div64(most, 1024) : 64);
-  k_resample_moves<<<blocks, 256, 0, stream>>>(mv);
-  return launch_status();
-}
-
 }  // namespace resample
 }  // namespace gsdr
 
@@ -377,89 +362,53 @@ struct gsdrxResampler_t {
   int32_t device = 0;
   size_t sb = 4;       // bytes per sample
   bool tiled = false;  // one launch a call (k_resample_tile<S, true>); else the seam plan through the one-shot calls
-  uint64_t consumed = 0;
-  uint64_t next_out = 0;
-  char* hist = nullptr;   // x[ceil(s / L) .. consumed), s = phase0 + next_out M (empty when that lies beyond)
-  char* spare = nullptr;  // the other history buffer (ping-pong)
-  char* seam = nullptr;   // seam plan: history + chunk head for the outputs that start in the history
+  gsdr::StreamState st;  // history: x[ceil(s / L) .. consumed), s = phase0 + next_out M
 };
 
 namespace gsdr {
 namespace resample {
 
-// p + n samples of sb bytes, n possibly negative: the origin of a virtual input, formed without stepping a pointer
-// outside its buffer (only addresses inside the chunk are ever read through it)
-static const char* offset_by(const char* p, int64_t n, size_t sb) {
-  return reinterpret_cast<const char*>(reinterpret_cast<uintptr_t>(p) + (uintptr_t)n * sb);
-}
-
 template <class S>
 static hipError_t process(gsdrxResampler_t& r, const StreamPlan& sp, const char* chunk, uint64_t len, S* out,
                           hipStream_t stream) {
-  const uint64_t Sx = r.consumed, words = sizeof(S) / 4;
-  uint64_t s = 0;
-  (void)stream_stuffed(r.phase0, r.M, r.T, r.next_out, &s);  // (the plan checked it)
-  // the next history: the tail of the chunk, or the tail of the old history and the whole chunk
-  Moves next;
-  if (sp.hist_after) {
-    uint64_t kept = 0;
-    if (sp.first_after < Sx) {
-      kept = Sx - sp.first_after;
-      next.add(r.spare, r.hist + (sp.first_after - sp.first) * sizeof(S), kept * words);
-    }
-    const uint64_t c0 = sp.first_after > Sx ? sp.first_after - Sx : 0;
-    next.add(r.spare + kept * sizeof(S), chunk + c0 * sizeof(S), (len - c0) * words);
+  const uint64_t s = r.phase0 + r.st.next_out * r.M;  // (the plan checked it)
+  if (sp.outputs == 0 || !r.tiled) {
+    // the seam plan through the one-shot calls (only samples to keep: its move launch alone)
+    const auto one_shot = [&](size_t, const char* in, uint64_t k, uint64_t n) {
+      return entry<S>(r.L, r.M, (uint32_t)((s + k * r.M) % r.L), r.taps, r.T, reinterpret_cast<const S*>(in), out + k, n,
+                      r.device, stream);
+    };
+    return stream_seam_plan(r.st, sp, chunk, len, sizeof(S), 1, stream, one_shot);
   }
-  if (sp.outputs == 0) return moves(next, stream);
-  if (r.tiled) {
-    // ONE launch: the one-shot call at output next_out (origin x[s / L], phase s mod L) over history ++ chunk
-    const uint64_t origin = s / r.L;
-    uint64_t extent = 0;
-    Plan pl{};
-    if (!stuffed_extent(s % r.L, r.M, r.T, sp.outputs, &extent) || !plan(r.L, r.M, r.T, sizeof(S), sp.outputs, &pl)) {
-      return hipErrorInvalidValue;
-    }
-    Params p{};
-    p.in = offset_by(chunk, (int64_t)(origin - Sx), sizeof(S));
-    p.taps = r.taps;
-    p.out = out;
-    p.N = sp.outputs;
-    p.need = inputs_for(r.L, extent);
-    p.phase = s % r.L;
-    p.T = r.T;
-    p.L = r.L;
-    p.M = r.M;
-    StreamArgs sa{};
-    sa.hist = r.hist;
-    sa.split = Sx > origin ? Sx - origin : 0;
-    sa.hist_first = (uint32_t)(sp.first - origin);  // 0 or 1
-    sa.next = next;
-    return launch<S>(p, pl, stream, &sa);
+  // ONE launch: the one-shot call at output next_out (origin x[s / L], phase s mod L) over history ++ chunk
+  const uint64_t Sx = r.st.consumed, origin = s / r.L;
+  uint64_t extent = 0;
+  Plan pl{};
+  if (!stuffed_extent(s % r.L, r.M, r.T, sp.outputs, &extent) || !plan(r.L, r.M, r.T, sizeof(S), sp.outputs, &pl)) {
+    return hipErrorInvalidValue;
   }
-  // the seam plan: history + chunk head gathered into the seam buffer (with the next history, one launch), then
-  // the outputs that start in the history and the remaining ones as two one-shot calls
-  Moves mv = next;
-  const uint64_t origin = s / r.L, lead = sp.first - origin;  // the seam buffer starts at x[origin]
-  if (sp.seam) {
-    uint64_t s_last = 0;
-    (void)stream_stuffed(r.phase0, r.M, r.T, r.next_out + sp.seam - 1, &s_last);
-    const uint64_t head = (s_last + r.T - 1) / r.L + 1 - Sx;  // chunk samples the last seam output reads
-    mv.add(r.seam + lead * sizeof(S), r.hist, sp.hist * words);
-    mv.add(r.seam + (lead + sp.hist) * sizeof(S), chunk, head * words);
+  Params p{};
+  p.in = offset_by(chunk, (int64_t)(origin - Sx), sizeof(S));
+  p.taps = r.taps;
+  p.out = out;
+  p.N = sp.outputs;
+  p.need = inputs_for(r.L, extent);
+  p.phase = s % r.L;
+  p.T = r.T;
+  p.L = r.L;
+  p.M = r.M;
+  StreamArgs sa{};
+  sa.hist = r.st.hist;
+  sa.split = Sx > origin ? Sx - origin : 0;
+  sa.hist_first = (uint32_t)sp.lead;  // 0 or 1
+  StreamMoves next;
+  stream_next_history(sp, len, &next);
+  for (int i = 0; i < next.n; ++i) {
+    const StreamMoves::Seg& m = next.seg[i];
+    sa.next.add(r.st.at(m.dst, chunk) + m.dst_off * sizeof(S), r.st.at(m.src, chunk) + m.src_off * sizeof(S),
+                m.count * (sizeof(S) / 4));
   }
-  hipError_t e = moves(mv, stream);
-  if (e == hipSuccess && sp.seam) {
-    e = entry<S>(r.L, r.M, (uint32_t)(s % r.L), r.taps, r.T, reinterpret_cast<const S*>(r.seam), out, sp.seam,
-                 r.device, stream);
-  }
-  if (e == hipSuccess && sp.outputs > sp.seam) {
-    uint64_t s_mid = 0;
-    (void)stream_stuffed(r.phase0, r.M, r.T, r.next_out + sp.seam, &s_mid);
-    const char* in = offset_by(chunk, (int64_t)(s_mid / r.L - Sx), sizeof(S));
-    e = entry<S>(r.L, r.M, (uint32_t)(s_mid % r.L), r.taps, r.T, reinterpret_cast<const S*>(in), out + sp.seam,
-                 sp.outputs - sp.seam, r.device, stream);
-  }
-  return e;
+  return launch<S>(p, pl, stream, &sa);
 }
 
 }  // namespace resample
@@ -487,12 +436,8 @@ GSDR_C_LINKAGE hipError_t gsdrxResamplerCreate(gsdrxResampler* resampler, int sa
     gsdr::resample::route_of(interpolation, decimation, numTaps, r->sb, &pl);
     r->tiled = pl.route == gsdr::resample::kRouteTile;
   }
-  gsdr::DeviceScope scope(cudaDevice);
-  hipError_t e = scope.status();
-  const size_t most = (size_t)gsdr::resample::ceil_div64(numTaps, interpolation);  // samples an output reads at most
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&r->hist), most * r->sb);  // history < most samples
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&r->spare), most * r->sb);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&r->seam), 2 * most * r->sb);  // 1 + 2 (most - 1)
+  const hipError_t e = r->st.alloc(cudaDevice, gsdr::stream_hist_capacity(interpolation, numTaps) * r->sb,
+                                   gsdr::stream_seam_capacity(interpolation, numTaps) * r->sb);
   if (e != hipSuccess) {
     (void)gsdrxResamplerDestroy(r);
     return e;
@@ -502,9 +447,9 @@ GSDR_C_LINKAGE hipError_t gsdrxResamplerCreate(gsdrxResampler* resampler, int sa
 }
 
 GSDR_C_LINKAGE size_t gsdrxResamplerOutputsFor(gsdrxResampler r, size_t numInputSamples) GSDR_NO_EXCEPT {
-  gsdr::resample::StreamPlan sp;
+  gsdr::StreamPlan sp;
   if (r == nullptr) return 0;
-  if (!gsdr::resample::stream_plan(r->L, r->M, r->T, r->phase0, r->consumed, r->next_out, numInputSamples, &sp)) return 0;
+  if (!gsdr::stream_plan(r->L, r->M, r->T, r->phase0, r->st.consumed, r->st.next_out, numInputSamples, &sp)) return 0;
   return (size_t)sp.outputs;
 }
 
@@ -515,8 +460,8 @@ GSDR_C_LINKAGE hipError_t gsdrxResamplerProcess(gsdrxResampler r, const void* in
   if (r == nullptr) return hipErrorInvalidValue;
   if (numInputSamples == 0) return hipSuccess;
   if (input == nullptr) return hipErrorInvalidValue;
-  gsdr::resample::StreamPlan sp;
-  if (!gsdr::resample::stream_plan(r->L, r->M, r->T, r->phase0, r->consumed, r->next_out, numInputSamples, &sp)) {
+  gsdr::StreamPlan sp;
+  if (!gsdr::stream_plan(r->L, r->M, r->T, r->phase0, r->st.consumed, r->st.next_out, numInputSamples, &sp)) {
     return hipErrorInvalidValue;
   }
   if (sp.outputs > outputCapacity || (sp.outputs && output == nullptr)) return hipErrorInvalidValue;
@@ -527,29 +472,14 @@ GSDR_C_LINKAGE hipError_t gsdrxResamplerProcess(gsdrxResampler r, const void* in
       r->sb == 8 ? gsdr::resample::process<float2>(*r, sp, chunk, numInputSamples, static_cast<float2*>(output), cudaStream)
                  : gsdr::resample::process<float>(*r, sp, chunk, numInputSamples, static_cast<float*>(output), cudaStream);
   if (e != hipSuccess) return e;
-  if (sp.hist_after) std::swap(r->hist, r->spare);
-  r->consumed += numInputSamples;
-  r->next_out += sp.outputs;
+  r->st.commit(sp, numInputSamples);
   if (numOutputsWritten) *numOutputsWritten = (size_t)sp.outputs;
   return hipSuccess;
 }
 
 GSDR_C_LINKAGE hipError_t gsdrxResamplerDestroy(gsdrxResampler r) GSDR_NO_EXCEPT {
   if (r == nullptr) return hipSuccess;
-  hipError_t e = hipSuccess;
-  {
-    gsdr::DeviceScope scope(r->device);
-    if (scope.status() == hipSuccess) {
-      for (char* b : {r->hist, r->spare, r->seam}) {
-        if (b) {
-          const hipError_t f = hipFree(b);
-          if (e == hipSuccess) e = f;
-        }
-      }
-    } else {
-      e = scope.status();
-    }
-  }
+  const hipError_t e = r->st.release(r->device);
   delete r;
   return e;
 }
@@ -558,8 +488,8 @@ GSDR_C_LINKAGE void gsdrxResamplerPlan(uint32_t interpolation, uint32_t decimati
                                        uint64_t consumed, uint64_t nextOutput, uint64_t chunk,
                                        uint64_t plan[6]) GSDR_NO_EXCEPT {
   if (plan == nullptr) return;
-  gsdr::resample::StreamPlan sp;
-  (void)gsdr::resample::stream_plan(interpolation, decimation, numTaps, phase, consumed, nextOutput, chunk, &sp);
+  gsdr::StreamPlan sp;
+  (void)gsdr::stream_plan(interpolation, decimation, numTaps, phase, consumed, nextOutput, chunk, &sp);
   plan[0] = sp.outputs;  // (all zero when refused)
   plan[1] = sp.seam;
   plan[2] = sp.hist;

@@ -10,8 +10,9 @@
 // The launch runs the kernel one monolithic call would run, with the absolute index of output 0's first
 // sample as firstSampleIndex, so the NCO phase and the per-output MAC order are those of that call: the
 // outputs are bit-identical. Shapes without a one-launch kernel (runtime-decimation and generic kernels)
-// keep the older plan: a gather launch (seam = history + chunk head, next history), then the seam and the
-// main outputs as two filter calls.
+// keep the older plan (stream_seam_plan, stream_buffers.hpp): a gather launch (seam = history + chunk head, next
+// history), then the seam and the main outputs as two filter calls. Which outputs a call writes and where the kept
+// samples go is stream_plan.hpp (L = 1), shared with gsdrxResampler.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,7 +24,7 @@
 #include "gsdr/fm.h"
 #include "gsdr/gsdr_ext.h"
 #include "gsdr/stream.h"
-#include "launch.hpp"
+#include "stream_buffers.hpp"
 #include "stream_step.hpp"
 
 struct gsdrxStream_t {
@@ -38,11 +39,7 @@ struct gsdrxStream_t {
   int32_t device = 0;
   size_t sb = 8;  // bytes per input sample
   size_t ob = 8;  // bytes per output
-  uint64_t consumed = 0;
-  uint64_t next_out = 0;
-  char* hist = nullptr;   // samples [next_out * D, consumed) (empty if next_out * D >= consumed)
-  char* spare = nullptr;  // the other history buffer (ping-pong)
-  char* seam = nullptr;   // history + chunk head for the seam outputs
+  gsdr::StreamState st;  // history: samples [next_out * D, consumed) (empty if next_out * D >= consumed)
   // channels of one RF input (gsdrxStreamCreateMulti; one channel for gsdrxStreamCreate): frequency and
   // deviation per channel, channel c's outputs at output + c * outputCapacity
   std::vector<float> chans, devs;
@@ -51,25 +48,8 @@ struct gsdrxStream_t {
 namespace gsdr {
 namespace {
 
-struct Plan {
-  uint64_t n_seam, head, n_main, main_off, hist_after, m_mid, m_end;
-};
-
-Plan make_plan(uint32_t D, uint64_t W, uint64_t S, uint64_t m_next, uint64_t M) {
-  Plan p{};
-  const uint64_t S_new = S + M;
-  uint64_t m_end = S_new >= W ? (S_new - W) / D + 1 : 0;  // first output whose window is incomplete
-  m_end = std::max(m_end, m_next);
-  const uint64_t m_mid = std::min(std::max(ceil_div<uint64_t>(S, D), m_next), m_end);
-  p.m_mid = m_mid;
-  p.m_end = m_end;
-  p.n_seam = m_mid - m_next;
-  p.head = p.n_seam ? (m_mid - 1) * D + W - S : 0;  // chunk samples the last seam output reads
-  p.n_main = m_end - m_mid;
-  p.main_off = p.n_main ? m_mid * D - S : 0;
-  const uint64_t from = m_end * D;
-  p.hist_after = S_new > from ? S_new - from : 0;
-  return p;
+bool plan_of(const gsdrxStream_t& s, size_t chunk, StreamPlan* sp) {
+  return stream_plan(1, s.D, s.W, 0, s.st.consumed, s.st.next_out, chunk, sp);
 }
 
 hipError_t filter(const gsdrxStream_t& s, size_t c, const void* in, uint64_t first, void* out, size_t n,
@@ -106,7 +86,8 @@ hipError_t filter(const gsdrxStream_t& s, size_t c, const void* in, uint64_t fir
 // The small device-to-device moves of one call (seam = history + chunk head, next history = the tail of
 // old history + chunk), gathered into ONE launch: as separate hipMemcpyAsync calls each was a runtime blit
 // launch of ~4-5 us, four of them per call, which is what a short float call paid (tools/float_stream_time.py).
-// Segments never overlap (they write seam / spare and read hist / the chunk).
+// Segments never overlap (they write seam / spare and read hist / the chunk). A move list of stream_plan.hpp
+// resolved against an object's pointers, in bytes: an int8 I/Q sample is 2 of them.
 struct Gather {
   static constexpr int kMax = 4;
   struct Seg {
@@ -136,15 +117,6 @@ __global__ __launch_bounds__(256) void k_stream_gather(Gather g) {
   }
 }
 
-hipError_t gather(const Gather& g, hipStream_t st) {
-  if (g.n == 0) return hipSuccess;
-  uint64_t most = 0;
-  for (int i = 0; i < g.n; ++i) most = std::max<uint64_t>(most, g.seg[i].bytes);
-  const uint32_t blocks = (uint32_t)std::min<uint64_t>(64, ceil_div<uint64_t>(most, 256u * 4u));
-  k_stream_gather<<<blocks, 256, 0, st>>>(g);
-  return launch_status();
-}
-
 // One channel's one-launch step: int8 I/Q at decimation 4 on the matrix cores, every other shape on the tiled
 // kernels (the same kernels as one monolithic call, tile for tile). hipErrorNotSupported, with nothing
 // launched: the shape has no one-launch step.
@@ -154,7 +126,7 @@ hipError_t channel_step(const gsdrxStream_t& s, const ChainSpec& cs, size_t c, c
   hipError_t e = hipErrorNotSupported;
   if (s.kind == GSDRX_STREAM_FIR) {
     hipFloatComplex* o = static_cast<hipFloatComplex*>(out);
-    if (i8) e = fir_int8_stream_step(s.next_out, s.D, s.taps, s.T, so, o, n, s.device, st);
+    if (i8) e = fir_int8_stream_step(s.st.next_out, s.D, s.taps, s.T, so, o, n, s.device, st);
     if (e != hipErrorNotSupported) return e;
     return i8 ? fir_int8_stream_step_tiled(s.D, s.taps, s.T, so, o, n, s.device, st)
               : fir_fc_stream_step(s.D, s.taps, s.T, so, o, n, s.device, st);
@@ -170,22 +142,34 @@ hipError_t channel_step(const gsdrxStream_t& s, const ChainSpec& cs, size_t c, c
 }
 
 }  // namespace
+
+hipError_t stream_move(const StreamState& b, const StreamMoves& mv, const void* chunk, size_t sb, hipStream_t st) {
+  if (mv.n == 0) return hipSuccess;
+  Gather g;
+  uint64_t most = 0;
+  for (int i = 0; i < mv.n; ++i) {
+    const StreamMoves::Seg& m = mv.seg[i];
+    g.add(b.at(m.dst, chunk) + m.dst_off * sb, b.at(m.src, chunk) + m.src_off * sb, m.count * sb);
+    most = std::max<uint64_t>(most, m.count * sb);
+  }
+  const uint32_t blocks = (uint32_t)std::min<uint64_t>(64, ceil_div<uint64_t>(most, 256u * 4u));
+  k_stream_gather<<<blocks, 256, 0, st>>>(g);
+  return launch_status();
+}
+
 }  // namespace gsdr
 
-using gsdr::Plan;
+using gsdr::StreamPlan;
 
 GSDR_C_LINKAGE void gsdrxStreamPlan(uint32_t decimation, size_t window, uint64_t consumed, uint64_t nextOutput,
                                     size_t chunk, uint64_t plan[5]) GSDR_NO_EXCEPT {
   if (plan == nullptr) return;
-  if (decimation == 0 || window == 0) {
-    for (int i = 0; i < 5; ++i) plan[i] = 0;
-    return;
-  }
-  const Plan p = gsdr::make_plan(decimation, window, consumed, nextOutput, chunk);
-  plan[0] = p.n_seam;
+  StreamPlan p;
+  (void)gsdr::stream_plan(1, decimation, window, 0, consumed, nextOutput, chunk, &p);
+  plan[0] = p.seam;  // (all zero when refused)
   plan[1] = p.head;
-  plan[2] = p.n_main;
-  plan[3] = p.main_off;
+  plan[2] = p.outputs - p.seam;
+  plan[3] = (uint64_t)p.main_off;
   plan[4] = p.hist_after;
 }
 
@@ -222,13 +206,8 @@ hipError_t create_stream(gsdrxStream* stream, int kind, int sampleFormat, uint32
   s->device = cudaDevice;
   s->sb = sampleFormat == GSDRX_SAMPLES_CS8 ? 2 : 8;
   s->ob = (kind == GSDRX_STREAM_FIR || kind == GSDRX_STREAM_XLATE) ? 8 : 4;
-  DeviceScope scope(cudaDevice);
-  hipError_t e = scope.status();
-  const size_t hist_bytes = s->W * s->sb;  // history < W samples
-  const size_t seam_bytes = 2 * s->W * s->sb;
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->hist), hist_bytes);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->spare), hist_bytes);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->seam), seam_bytes);
+  const hipError_t e =
+      s->st.alloc(cudaDevice, stream_hist_capacity(1, s->W) * s->sb, stream_seam_capacity(1, s->W) * s->sb);
   if (e != hipSuccess) {
     (void)gsdrxStreamDestroy(s);
     return e;
@@ -270,9 +249,8 @@ GSDR_C_LINKAGE hipError_t gsdrxStreamCreateMulti(gsdrxStream* stream, int kind, 
 }
 
 GSDR_C_LINKAGE size_t gsdrxStreamOutputsFor(gsdrxStream s, size_t numInputSamples) GSDR_NO_EXCEPT {
-  if (s == nullptr) return 0;
-  const Plan p = gsdr::make_plan(s->D, s->W, s->consumed, s->next_out, numInputSamples);
-  return p.n_seam + p.n_main;
+  StreamPlan p;
+  return s != nullptr && gsdr::plan_of(*s, numInputSamples, &p) ? (size_t)p.outputs : 0;
 }
 
 GSDR_C_LINKAGE hipError_t gsdrxStreamProcess(gsdrxStream s, const void* input, size_t numInputSamples, void* output,
@@ -282,8 +260,9 @@ GSDR_C_LINKAGE hipError_t gsdrxStreamProcess(gsdrxStream s, const void* input, s
   if (s == nullptr) return hipErrorInvalidValue;
   if (numInputSamples == 0) return hipSuccess;
   if (input == nullptr) return hipErrorInvalidValue;
-  const Plan p = gsdr::make_plan(s->D, s->W, s->consumed, s->next_out, numInputSamples);
-  const size_t n_out = p.n_seam + p.n_main;
+  StreamPlan p;
+  if (!gsdr::plan_of(*s, numInputSamples, &p)) return hipErrorInvalidValue;
+  const size_t n_out = (size_t)p.outputs;
   if (n_out > outputCapacity || (n_out && output == nullptr)) return hipErrorInvalidValue;
   gsdr::DeviceScope scope(s->device);
   if (scope.status() != hipSuccess) return scope.status();
@@ -291,9 +270,8 @@ GSDR_C_LINKAGE hipError_t gsdrxStreamProcess(gsdrxStream s, const void* input, s
   char* out = static_cast<char*>(output);
   const size_t C = s->chans.size();
   const size_t ostride = outputCapacity * s->ob;  // bytes between channels' output blocks
-  const uint64_t S = s->consumed, h0 = s->next_out * s->D;
-  const uint64_t h = S > h0 ? S - h0 : 0;
-  hipError_t e = hipSuccess;
+  const uint64_t S = s->st.consumed, h0 = p.first;  // = next_out * D
+  hipError_t e = hipErrorNotSupported;  // (no one-launch step yet)
   if (n_out > 0) {
     // ONE launch (per channel, or per 16 channels on the grouped kernel) does the seam outputs (their samples
     // before the chunk read from the history buffer), the direct outputs and the next history copy: the int8
@@ -303,17 +281,16 @@ GSDR_C_LINKAGE hipError_t gsdrxStreamProcess(gsdrxStream s, const void* input, s
     so.chunk = chunk;
     so.chunk_len = numInputSamples;
     so.in_off = (int64_t)h0 - (int64_t)S;
-    so.hist = s->hist;
-    so.hist_len = h;
-    so.hist_out = s->spare;
-    so.hist_from = (int64_t)(p.m_end * s->D) - (int64_t)S;
+    so.hist = s->st.hist;
+    so.hist_len = p.hist;
+    so.hist_out = s->st.spare;
+    so.hist_from = (int64_t)p.first_after - (int64_t)S;
     so.hist_n = p.hist_after;
     // (the chain part is unused by a FIR stream)
     const int mode = s->kind == GSDRX_STREAM_FM      ? gsdr::kModeFm
                      : s->kind == GSDRX_STREAM_XLATE ? gsdr::kModeIq
                                                      : gsdr::kModeAm;
     const gsdr::ChainSpec cs{mode, s->fs, s->tune, s->D, s->n0 + h0, s->taps, s->T};
-    e = hipErrorNotSupported;
     if (C > 1 && s->format != GSDRX_SAMPLES_CS8) {
       gsdr::ChainMultiStep* step =
           s->kind == GSDRX_STREAM_XLATE ? gsdr::xlate_multi_stream_step : gsdr::chain_multi_stream_step;
@@ -333,65 +310,24 @@ GSDR_C_LINKAGE hipError_t gsdrxStreamProcess(gsdrxStream s, const void* input, s
       }
       if (c + 1 == C) e = hipSuccess;
     }
-    if (e == hipSuccess) {
-      std::swap(s->hist, s->spare);
-      s->consumed += numInputSamples;
-      s->next_out = p.m_end;
-      if (numOutputsWritten) *numOutputsWritten = n_out;
-      return hipSuccess;
-    }
-    if (e != hipErrorNotSupported) return e;
-    e = hipSuccess;  // not this shape: the seam path below
   }
-  // every small move of the call (seam assembly, next history) in one launch ahead of the filters
-  gsdr::Gather g;
-  if (p.n_seam) {
-    g.add(s->seam, s->hist, h * s->sb);
-    g.add(s->seam + h * s->sb, chunk, p.head * s->sb);
+  if (e == hipErrorNotSupported) {
+    // not this shape, or only samples to keep: the seam plan through the filter calls
+    e = gsdr::stream_seam_plan(s->st, p, chunk, numInputSamples, s->sb, C, cudaStream,
+                               [&](size_t c, const char* in, uint64_t k, uint64_t n) {
+                                 return gsdr::filter(*s, c, in, s->n0 + h0 + k * s->D, out + c * ostride + k * s->ob, n,
+                                                     cudaStream);
+                               });
   }
-  if (p.hist_after) {
-    const uint64_t from = p.m_end * s->D, S_new = S + numInputSamples;
-    uint64_t done = 0;
-    if (from < S) {  // part of the new history is still in the old one
-      done = S - from;
-      g.add(s->spare, s->hist + (from - h0) * s->sb, done * s->sb);
-    }
-    const uint64_t c0 = from > S ? from - S : 0;
-    g.add(s->spare + done * s->sb, chunk + c0 * s->sb, (S_new - S - c0) * s->sb);
-  }
-  e = gsdr::gather(g, cudaStream);
-  for (size_t c = 0; c < C && e == hipSuccess; ++c) {
-    char* oc = out + c * ostride;
-    if (p.n_seam) e = gsdr::filter(*s, c, s->seam, s->n0 + h0, oc, p.n_seam, cudaStream);
-    if (e == hipSuccess && p.n_main) {
-      e = gsdr::filter(*s, c, chunk + p.main_off * s->sb, s->n0 + p.m_mid * s->D, oc + p.n_seam * s->ob, p.n_main,
-                       cudaStream);
-    }
-  }
-  if (e == hipSuccess && p.hist_after) std::swap(s->hist, s->spare);
   if (e != hipSuccess) return e;
-  s->consumed += numInputSamples;
-  s->next_out = p.m_end;
+  s->st.commit(p, numInputSamples);
   if (numOutputsWritten) *numOutputsWritten = n_out;
   return hipSuccess;
 }
 
 GSDR_C_LINKAGE hipError_t gsdrxStreamDestroy(gsdrxStream s) GSDR_NO_EXCEPT {
   if (s == nullptr) return hipSuccess;
-  hipError_t e = hipSuccess;
-  {
-    gsdr::DeviceScope scope(s->device);
-    if (scope.status() == hipSuccess) {
-      for (char* b : {s->hist, s->spare, s->seam}) {
-        if (b) {
-          const hipError_t f = hipFree(b);
-          if (e == hipSuccess) e = f;
-        }
-      }
-    } else {
-      e = scope.status();
-    }
-  }
+  const hipError_t e = s->st.release(s->device);
   delete s;
   return e;
 }

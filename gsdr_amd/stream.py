@@ -27,7 +27,39 @@ from .ops import stream_of
 KINDS = {"fir": 0, "fm": 1, "am": 2, "xlate": 4}  # (3 is unassigned, stream.h)
 
 
-class Stream:
+class _Handle:
+    """What Stream and Resampler share: the library handle's lifetime and the tail of process()."""
+
+    _prefix = ""  # gsdrxStream / gsdrxResampler: the entry points are <prefix>OutputsFor / Process / Destroy
+
+    def outputs_for(self, num_samples: int) -> int:
+        return getattr(lib, self._prefix + "OutputsFor")(self._h, num_samples)
+
+    def _process(self, x: torch.Tensor, n_in: int, out: torch.Tensor, n_out: int, capacity: int) -> None:
+        """The call on x's stream; the count it reports must be the one outputs_for gave."""
+        name = self._prefix + "Process"
+        written = ctypes.c_size_t(0)
+        check(name, getattr(lib, name)(self._h, x.data_ptr() if n_in else None, n_in, out.data_ptr() if n_out else None,
+                                       capacity, ctypes.byref(written), stream_of(x)))
+        if written.value != n_out:
+            raise GsdrError(name, -1)
+
+    def close(self):
+        if self._h:
+            name = self._prefix + "Destroy"
+            check(name, getattr(lib, name)(self._h))
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Stream(_Handle):
+    _prefix = "gsdrxStream"
+
     def __init__(self, kind: str, taps: torch.Tensor, decimation: int, rf_sample_rate: float = 1.0,
                  tuning_frequency: float = 0.0, channel_frequency: float = 0.0, frequency_deviation: float = 1.0,
                  first_sample_index: int = 0, int8: bool = False):
@@ -57,9 +89,6 @@ class Stream:
                 rf_sample_rate, tuning_frequency, channel_frequency, frequency_deviation, first_sample_index,
                 self.device.index))
 
-    def outputs_for(self, num_samples: int) -> int:
-        return lib.gsdrxStreamOutputsFor(self._h, num_samples)
-
     def process(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         want = torch.int8 if self.int8 else torch.complex64
         if x.dtype != want or not x.is_contiguous() or x.device != self.device:
@@ -80,27 +109,11 @@ class Stream:
             if out.dtype != odt or out.numel() < n_out:
                 raise ValueError(f"output must hold {n_out} {odt} values")
             cap = out.numel()
-        written = ctypes.c_size_t(0)
-        check("gsdrxStreamProcess", lib.gsdrxStreamProcess(self._h, x.data_ptr() if n_in else None, n_in,
-                                                           out.data_ptr() if n_out else None, cap,
-                                                           ctypes.byref(written), stream_of(x)))
-        if written.value != n_out:
-            raise GsdrError("gsdrxStreamProcess", -1)
+        self._process(x, n_in, out, n_out, cap)
         return out[..., :n_out]
 
-    def close(self):
-        if self._h:
-            check("gsdrxStreamDestroy", lib.gsdrxStreamDestroy(self._h))
-            self._h = ctypes.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Resampler:
+class Resampler(_Handle):
     """gsdrxResampler (include/gsdr/resampler.h): the stream form of ops.resample.
 
         r = Resampler(taps, interpolation=24, decimation=125)
@@ -109,6 +122,8 @@ class Resampler:
 
     Concatenated over the calls, the outputs equal one gsdrxResampleFF / FC call over the concatenated input, bit
     for bit."""
+
+    _prefix = "gsdrxResampler"
 
     def __init__(self, taps: torch.Tensor, interpolation: int, decimation: int, phase: int = 0,
                  complex_samples: bool = False):
@@ -125,9 +140,6 @@ class Resampler:
             ctypes.byref(self._h), 1 if complex_samples else 0, L, M, q, taps.data_ptr(), taps.numel(),
             self.device.index))
 
-    def outputs_for(self, num_samples: int) -> int:
-        return lib.gsdrxResamplerOutputsFor(self._h, num_samples)
-
     def process(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         if x.dtype != self.dtype or not x.is_contiguous() or x.device != self.device:
             raise TypeError(f"input must be a contiguous {self.dtype} tensor on {self.device}")
@@ -137,24 +149,8 @@ class Resampler:
             out = torch.empty(n_out, dtype=self.dtype, device=self.device)
         if out.dtype != self.dtype or out.numel() < n_out or not out.is_contiguous() or out.device != self.device:
             raise ValueError(f"output must be a contiguous tensor of at least {n_out} {self.dtype} values on {self.device}")
-        written = ctypes.c_size_t(0)
-        check("gsdrxResamplerProcess", lib.gsdrxResamplerProcess(self._h, x.data_ptr() if n_in else None, n_in,
-                                                                 out.data_ptr() if n_out else None, out.numel(),
-                                                                 ctypes.byref(written), stream_of(x)))
-        if written.value != n_out:
-            raise GsdrError("gsdrxResamplerProcess", -1)
+        self._process(x, n_in, out, n_out, out.numel())
         return out.view(-1)[:n_out]
-
-    def close(self):
-        if self._h:
-            check("gsdrxResamplerDestroy", lib.gsdrxResamplerDestroy(self._h))
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def resampler_plan(interpolation: int, decimation: int, num_taps: int, phase: int, consumed: int, next_output: int,

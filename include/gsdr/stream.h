@@ -105,7 +105,10 @@ GSDR_C_LINKAGE GSDR_PUBLIC hipError_t gsdrxStreamCreateMulti(
     size_t firstSampleIndex,
     int32_t cudaDevice) GSDR_NO_EXCEPT;
 
-/** Number of outputs (per channel) the next gsdrxStreamProcess call with `numInputSamples` samples will write. */
+/**
+ * Number of outputs (per channel) the next gsdrxStreamProcess call with `numInputSamples` samples will write; 0 for
+ * a call that gsdrxStreamProcess refuses (below).
+ */
 GSDR_C_LINKAGE GSDR_PUBLIC size_t gsdrxStreamOutputsFor(gsdrxStream stream, size_t numInputSamples) GSDR_NO_EXCEPT;
 
 /**
@@ -114,7 +117,10 @@ GSDR_C_LINKAGE GSDR_PUBLIC size_t gsdrxStreamOutputsFor(gsdrxStream stream, size
  * (a multi-channel stream: channel c's at output + c * outputCapacity).
  * `*numOutputsWritten` receives the count (host-known, no synchronisation). Asynchronous on
  * `cudaStream`; the input chunk may be reused once the stream's work has completed. Returns
- * hipErrorInvalidValue, leaving the stream unchanged, when outputCapacity is too small.
+ * hipErrorInvalidValue, leaving the stream unchanged, when outputCapacity is too small, and when the samples consumed
+ * plus numInputSamples would leave 64 bits or the index m * decimation + W (W = the samples one output needs:
+ * tapCount, for FM tapCount + decimation) of an output of this call or of the next one would leave 63 bits. (Until
+ * the plan became the one gsdrxResampler uses, such positions wrapped silently.)
  * On any other error (a launch failing) the stream's state is also left unchanged -- the same chunk can
  * be passed again -- but the contents of `output` are unspecified: a multi-channel stream launches its
  * channels (or groups of 16) in turn, and the launches before the failing one have written their
@@ -138,7 +144,8 @@ GSDR_C_LINKAGE GSDR_PUBLIC hipError_t gsdrxStreamDestroy(gsdrxStream stream) GSD
  * next output, chunk length. plan[0] = seam outputs (computed from history + chunk head),
  * plan[1] = samples of the chunk head copied behind the history for them, plan[2] = outputs computed
  * directly from the chunk, plan[3] = chunk offset of the first direct output's window,
- * plan[4] = history length after the call.
+ * plan[4] = history length after the call. All five are 0 for arguments the object rejects (D or W == 0, consumed +
+ * chunk leaving 64 bits, an index that leaves 63 bits) and for a null `plan` nothing is written.
  */
 GSDR_C_LINKAGE GSDR_PUBLIC void gsdrxStreamPlan(
     uint32_t decimation,

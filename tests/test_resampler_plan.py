@@ -1,4 +1,4 @@
-"""CPU: the host plan of the streaming resampler (gsdrxResamplerPlan, gsdr_amd/csrc/resample_stream_plan.hpp) against
+"""CPU: the host plan of the streaming resampler (gsdrxResamplerPlan, gsdr_amd/csrc/stream_plan.hpp) against
 a brute-force model written here from the definitions of include/gsdr/resampler.h, and the argument checks of the
 gsdrxResampler entry points that return before any device work.
 

@@ -53,3 +53,36 @@ def test_plan_matches_brute_force(D, W):
             S, m_next = S_new, m_end
         assert produced == list(range(len(produced)))
         assert produced == brute(D, W, 0, 0, S)
+
+
+@pytest.mark.parametrize("D,W", [(1, 1), (1, 63), (4, 127), (4, 131), (3, 200), (8, 8), (16, 5), (5, 1)])
+def test_plan_is_the_resampler_plan_at_interpolation_one(D, W):
+    """One plan serves both objects (gsdr_amd/csrc/stream_plan.hpp): gsdrxStreamPlan(D, W, S, m, c) is
+    gsdrxResamplerPlan(L = 1, M = D, T = W, phase 0, S, m, c) read as (seam, head, outputs - seam, offset, history)."""
+    from gsdr_amd.stream import resampler_plan
+
+    rng = np.random.default_rng(D * 1000 + W + 7)
+    for trial in range(40):
+        S, m = 0, 0
+        for call in range(30):
+            c = max(int(rng.choice([0, 1, 2, W - 1, W, W + 1, int(rng.integers(0, 4 * W + 40))])), 0)
+            outputs, seam, hist, skip, hist_after, skip_after = resampler_plan(1, D, W, 0, S, m, c)
+            n_main = outputs - seam
+            want = (seam, (m + seam - 1) * D + W - S if seam else 0, n_main, (m + seam) * D - S if n_main else 0,
+                    hist_after)
+            assert plan(D, W, S, m, c) == want, (D, W, S, m, c)
+            assert hist == max(S - m * D, 0) and skip == min(max(m * D - S, 0), c)
+            S, m = S + c, m + outputs
+
+
+def test_plan_refuses_positions_that_leave_64_bits():
+    zero = (0,) * 5
+    assert plan(4, 127, (1 << 64) - 1, 0, 1) == zero                 # consumed + chunk leaves 64 bits
+    m = ((1 << 63) - 127) // 4 + 1                                   # the first m with m D + W >= 2^63
+    assert m * 4 + 127 >= 1 << 63 > (m - 1) * 4 + 127
+    assert plan(4, 127, 0, m, 100) == zero
+    from gsdr_amd.stream import resampler_plan
+
+    assert resampler_plan(1, 4, 127, 0, 0, m, 100) == (0,) * 6
+    assert resampler_plan(1, 4, 127, 0, 0, m - 1, 100)[5] == (m - 1) * 4 - 100   # the last position is taken
+    assert plan(0, 127, 0, 0, 100) == zero and plan(4, 0, 0, 0, 100) == zero
