@@ -120,6 +120,18 @@ hipError_t launch_fc_probe(const FirJob& j, hipStream_t s) {
       return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, 64, true>(j, s);
     case 141:
       return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, 66, true>(j, s);
+    // Round-7 pieces of the default kernel taken out one at a time (results unchanged):
+    // 150 the carried window rows, 151 the whole-chunk tap batch, 152 the row-base staging loads, 153 all three
+    // (the kernel as it was before them)
+    case 150:
+      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblNoCarry, true>(j, s);
+    case 151:
+      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblColumnTaps, true>(j, s);
+    case 152:
+      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblPlainRows, true>(j, s);
+    case 153:
+      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblNoCarry | kAblColumnTaps | kAblPlainRows, true>(
+          j, s);
     case 110:
     case 111:
       return launch_stream_probe(j, s, j.variant == 111);

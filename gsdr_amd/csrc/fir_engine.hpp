@@ -151,8 +151,9 @@ struct TapBuf {
 };
 
 // A window of the tap array starting at tap `base` (wave-uniform): the descriptor is re-based so
-// every tap inside the window is an immediate offset, which lets the compiler merge neighbouring
-// taps into s_buffer_load_dwordx2/x4/x8 and wait for the whole batch once.
+// every tap inside the window is an immediate offset. Read tap by tap (tap_at), neighbouring taps merge into
+// s_buffer_load_dwordx2/x4/x8, in batches the compiler sizes and each ends with a full lgkmcnt(0) drain (the
+// polyphase core read a column's 32 taps as eight batches of four dwordx2); TapChunk below reads a whole chunk.
 template <class TapT>
 __device__ __forceinline__ TapBuf tap_window(const void* taps, uint32_t T, uint32_t base) {
   const uint64_t a = reinterpret_cast<uint64_t>(reinterpret_cast<const TapT*>(taps) + base);
@@ -173,6 +174,44 @@ template <>
 __device__ __forceinline__ float2 tap_at<float2>(const TapBuf& tb, int i) {
   return make_float2(gsdr_s_buffer_load_f32(tb.rsrc, i * 8, 0), gsdr_s_buffer_load_f32(tb.rsrc, i * 8 + 4, 0));
 }
+
+// A whole tap chunk at once (the polyphase core): the chunk's taps are contiguous, so they are fetched as
+// s_buffer_load_dwordx16 (the widest form; merged single loads stop at x8) into NQ * 16 SGPRs and waited for ONCE,
+// before the chunk's first window read. Scalar loads return out of order and share their counter with LDS, so a wait
+// for a tap is always a full drain of that counter: with the taps settled up front, every later wait of the chunk
+// is a counted one on the in-order LDS reads alone.
+typedef float gsdr_f32x16 __attribute__((ext_vector_type(16)));
+__device__ gsdr_f32x16 gsdr_s_buffer_load_f32x16(gsdr_v4i32 rsrc, int offset, int aux) __asm(
+    "llvm.amdgcn.s.buffer.load.v16f32");
+
+template <int NQ>
+struct TapChunk {
+  gsdr_f32x16 q[NQ];
+  __device__ __forceinline__ void load(const TapBuf& tb) {
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) q[i] = gsdr_s_buffer_load_f32x16(tb.rsrc, i * 64, 0);
+  }
+  // The taps are "used" here, so the one wait for them lands here; no LDS read moves above it.
+  __device__ __forceinline__ void settle() {
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) asm volatile("" : "+s"(q[i])::"memory");
+  }
+  // tap `i` of the chunk (a compile-time constant after unrolling)
+  template <class TapT>
+  __device__ __forceinline__ TapT at(int i) const {
+    if constexpr (std::is_same<TapT, float>::value) {
+      return q[i / 16][i % 16];
+    } else {
+      return make_float2(q[(2 * i) / 16][(2 * i) % 16], q[(2 * i + 1) / 16][(2 * i + 1) % 16]);
+    }
+  }
+};
+// dwords of a chunk of `taps` taps, and whether it is fetched whole (1, 2 or 4 x16 loads: up to 64 SGPRs)
+template <class TapT>
+constexpr int tap_chunk_dwords(int taps) {
+  return taps * (int)(sizeof(TapT) / 4);
+}
+constexpr bool tap_chunk_whole(int dwords) { return dwords == 16 || dwords == 32 || dwords == 64; }
 
 // ------------------------------------------------------------------------------------------------
 // Launch parameters (one struct for every mode; passed by value)
@@ -504,6 +543,29 @@ __device__ __forceinline__ void load_batch(float4 (&v)[SB], const InT* __restric
   }
 }
 
+// The same batch for body rows row0 .. row0 + SB - 1 of an aligned, wholly readable tile of 16-byte quads (granule
+// (row0 + k) WG + tid): each row's address is a wave-uniform 64-bit base (scalar adds) plus the thread's one 32-bit
+// byte offset, the same register for every row (global_load ... vgpr, sgpr pair). Rows are WG * 16 bytes apart,
+// past the 12-bit immediate offset, and written as base[g0 + k WG] the compiler adds k WG * 16 to the thread's 64-bit
+// address in VALU pairs (v_add_co, a wait state, v_addc) row by row. The empty asm keeps each row base a scalar of
+// its own.
+typedef __attribute__((address_space(1))) gsdr_f32x4 GlobalQuad;
+typedef __attribute__((address_space(1))) char GlobalByte;
+template <int SB, int WG, bool NT>
+__device__ __forceinline__ void load_rows(float4 (&v)[SB], const float4* __restrict__ base, int row0, uint32_t tid) {
+  const uint32_t boff = tid * 16u;  // the thread's byte offset in every row
+#pragma unroll
+  for (int k = 0; k < SB; ++k) {
+    // (the row base goes through the asm as an integer and comes back as a global-memory pointer: a laundered
+    // generic pointer would make these flat loads)
+    uint64_t rb = reinterpret_cast<uint64_t>(base + (row0 + k) * WG);
+    asm("" : "+s"(rb));
+    const GlobalQuad* __restrict__ g = reinterpret_cast<const GlobalQuad*>(reinterpret_cast<const GlobalByte*>(rb) + boff);
+    const gsdr_f32x4 q = NT ? __builtin_nontemporal_load(g) : *g;
+    v[k] = make_float4(q.x, q.y, q.z, q.w);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Staging mixers: what stage_tile does to a granule between its load and its LDS store. A thread's tile granules
 // are g = k WG + tid, row k = 0, 1, ...; stage_tile hands each of them to its mixer once, in ascending row order:
@@ -724,7 +786,8 @@ __device__ __forceinline__ void stage_history(float4* __restrict__ lds, const In
 // off 16; int8 I/Q: 2 bytes off 4) at every tile start. The tile body is then loaded as aligned 16-byte granules
 // starting one sample early, and each loaded pair is split over two LDS granules (second half of slot g - 1, first
 // half of slot g); the halo re-writes the body's last slot whole.
-template <class InT, class Geo, int WG, bool VEC, bool NT = false, bool DMA = false, int SH = 0, class Mix>
+template <class InT, class Geo, int WG, bool VEC, bool NT = false, bool DMA = false, int SH = 0, bool ROWS = true,
+          class Mix>
 __device__ __forceinline__ void stage_tile(float4* __restrict__ lds, const InT* __restrict__ in, uint64_t S0,
                                            uint32_t NG, const FirParams& p, Mix m) {
   constexpr int G = Geo::G;
@@ -828,7 +891,11 @@ __device__ __forceinline__ void stage_tile(float4* __restrict__ lds, const InT* 
     for (int b0 = 0; b0 < BPT; b0 += SB) {
       float4 v[SB];
       if (whole) {
-        load_batch<InT, SB, WG, NT>(v, in + S0, b0 * WG + tid);
+        if constexpr (ROWS && !std::is_same<InT, Iq8>::value) {
+          load_rows<SB, WG, NT>(v, reinterpret_cast<const float4*>(in + S0), b0, tid);
+        } else {
+          load_batch<InT, SB, WG, NT>(v, in + S0, b0 * WG + tid);
+        }
       } else {
 #pragma unroll
         for (int k = 0; k < SB; ++k) {
@@ -1097,8 +1164,16 @@ __device__ __forceinline__ void tile_epilogue(const FirParams& p, uint64_t out0,
 // ------------------------------------------------------------------------------------------------
 // Polyphase compute core shared by the polyphase kernels: thread t accumulates its R outputs from
 // the staged tile in LDS. JC = tap rows per chunk (a multiple of R); a chunk covers JC*D taps.
+//   * Taps: the whole chunk in one scalar batch, settled before the first window read (TapChunk), where the chunk
+//     is 16, 32 or 64 dwords; other shapes fetch them per column.
+//   * Window: column h of chunk c is rows u = 0 .. R+JC-2 of that column, and its last R-1 rows are the first R-1
+//     rows of the same column in chunk c+1 (the chunk advances JC rows). Those granules stay in registers across the
+//     other columns instead of being read from LDS again: (R-1) * CPR granules carried, (R-1) of R+JC-1 reads a column
+//     saved in every chunk but the first. The first chunk is peeled, so which reads exist is fixed at compile time.
+//   The order of every accumulator's products (chunk c, column h, row j, element e) is untouched by either.
+// CARRY / BATCH = false (tuning probes): the core without the carried rows / with per-column tap batches.
 // ------------------------------------------------------------------------------------------------
-template <class TapT, class InT, int D, int R, int JC, int WG, bool LIGHT = false, bool FENCE = false>
+template <class TapT, class InT, int D, int R, int JC, int WG, bool LIGHT = false, bool CARRY = true, bool BATCH = true>
 __device__ __forceinline__ void poly_compute(const float4* __restrict__ lds, const FirParams& p,
                                              typename Product<TapT, InT>::type (&acc)[R]) {
   using Geo = TileGeo<InT, D, R, WG>;
@@ -1107,34 +1182,52 @@ __device__ __forceinline__ void poly_compute(const float4* __restrict__ lds, con
   static_assert(D % G == 0, "polyphase kernel needs whole granules per row");
   static_assert(JC % R == 0, "chunk rows must be whole thread segments");
   constexpr int NWIN = R + JC - 1;
+  constexpr int NCARRY = (CARRY && !LIGHT) ? R - 1 : 0;  // (JC >= R: the carried rows are the chunk's own reads)
+  constexpr int CHUNK_DW = tap_chunk_dwords<TapT>(JC * D);
+  constexpr bool WHOLE = BATCH && tap_chunk_whole(CHUNK_DW);
   const uint32_t t = threadIdx.x;
-  for (uint32_t c = 0; c < p.nch; ++c) {
+  float4 carry[CPR][NCARRY > 0 ? NCARRY : 1];
+  auto chunk = [&](uint32_t c, auto first) __attribute__((always_inline)) {
+    constexpr bool FIRST = decltype(first)::value;
     const float4* __restrict__ seg = lds + (t + c * (JC / R)) * Geo::SGP;
+    TapChunk<WHOLE ? CHUNK_DW / 16 : 1> tc;
+    if constexpr (WHOLE) {
+      tc.load(tap_window<TapT>(p.taps, p.T, c * JC * D));
+      tc.settle();
+    }
 #pragma unroll
     for (int h = 0; h < CPR; ++h) {
-      // taps first (one SMEM batch, one wait), then the LDS window (in-order, counted waits)
       TapT tv[JC][G];
-      const TapBuf tb = tap_window<TapT>(p.taps, p.T, c * JC * D + h * G);
+      if constexpr (WHOLE) {
 #pragma unroll
-      for (int j = 0; j < JC; ++j) {
+        for (int j = 0; j < JC; ++j) {
 #pragma unroll
-        for (int e = 0; e < G; ++e) tv[j][e] = tap_at<TapT>(tb, j * D + e);
+          for (int e = 0; e < G; ++e) tv[j][e] = tc.template at<TapT>(j * D + h * G + e);
+        }
+      } else {
+        const TapBuf tb = tap_window<TapT>(p.taps, p.T, c * JC * D + h * G);
+#pragma unroll
+        for (int j = 0; j < JC; ++j) {
+#pragma unroll
+          for (int e = 0; e < G; ++e) tv[j][e] = tap_at<TapT>(tb, j * D + e);
+        }
       }
-      // FENCE: keeps one column's window reads from being scheduled ahead of the previous column's
-      // multiply-adds (the persistent kernel's scheduler otherwise held every window at once)
-      if constexpr (FENCE) asm volatile("" ::: "memory");
       float4 win[NWIN];
 #pragma unroll
       for (int u = 0; u < NWIN; ++u) {
         const int q = u * CPR + h;
         // LIGHT (tuning probe, wrong results): only the thread's own R rows come from LDS, the rest of
         // the window repeats them -- the same FMAs with 4/19 of the LDS reads
-        if (!LIGHT || u < R) {
-          win[u] = seg[q + Geo::PAD * (q / Geo::SG)];
-        } else {
+        if (LIGHT && u >= R) {
           win[u] = win[u - R];
+        } else if (!FIRST && u < NCARRY) {
+          win[u] = carry[h][u];
+        } else {
+          win[u] = seg[q + Geo::PAD * (q / Geo::SG)];
         }
       }
+#pragma unroll
+      for (int u = 0; u < NCARRY; ++u) carry[h][u] = win[JC + u];
 #pragma unroll
       for (int j = 0; j < JC; ++j) {
 #pragma unroll
@@ -1144,6 +1237,13 @@ __device__ __forceinline__ void poly_compute(const float4* __restrict__ lds, con
         }
       }
     }
+  };
+  if constexpr (NCARRY > 0) {
+    if (p.nch == 0) return;
+    chunk(0u, std::true_type{});
+    for (uint32_t c = 1; c < p.nch; ++c) chunk(c, std::false_type{});
+  } else {
+    for (uint32_t c = 0; c < p.nch; ++c) chunk(c, std::true_type{});
   }
 }
 
@@ -1256,8 +1356,13 @@ __device__ __forceinline__ bool all_finite(const float (&acc)[R]) {
 // ABL (ablation, tuning probes only): low bits 0 = full kernel, 1 = staging only, 2 = compute only;
 // chain-mode flags 8 = staging without the NCO mix, 16 = plain float store instead of the FM
 // discriminator, 64 = register window from the thread's own R rows only (wrong results: LDS-read probe).
+// The full kernel with one of its round-7 pieces taken out again (results unchanged): 128 = window rows shared by
+// consecutive chunks read from LDS again, 256 = taps fetched per column, 512 = tile-body loads addressed per thread.
 // NT: non-temporal (streaming) HBM loads for the staged input.
 // ------------------------------------------------------------------------------------------------
+constexpr int kAblWork = 127;  // the flags that change what the kernel computes
+constexpr int kAblNoCarry = 128, kAblColumnTaps = 256, kAblPlainRows = 512;
+
 // Tile of workgroup b. XCD-aware (XM): workgroups are dispatched round-robin over the 8 XCDs, so
 // with the identity map neighbouring tiles (which share a halo of input rows) sit on different L2s;
 // remapped, XCD x walks one contiguous range of tiles and the halo of the previous tile is still in
@@ -1302,10 +1407,10 @@ __device__ __forceinline__ void fir_poly_tile(const FirParams& p, uint32_t tile)
   const uint32_t sub = ANCH ? (p.cell_sub0 + tile) % SUBS : 0u;
   if constexpr ((ABL & 7) != 2) {
     if constexpr (ANCH && (ABL & 8) == 0) {
-      stage_tile<InT, Geo, WG, VEC, NT, DMA, SH>(
+      stage_tile<InT, Geo, WG, VEC, NT, DMA, SH, (ABL & kAblPlainRows) == 0>(
           lds, in, S0, NG, p, MixAnchored<WG>(p.nco_inc, sub * BPT, MODE == kModeFm ? sub * Geo::SG : 0u));
     } else {
-      stage_tile<InT, Geo, WG, VEC, NT, DMA, SH>(lds, in, S0, NG, p, MixNone{});
+      stage_tile<InT, Geo, WG, VEC, NT, DMA, SH, (ABL & kAblPlainRows) == 0>(lds, in, S0, NG, p, MixNone{});
     }
   }
   __syncthreads();
@@ -1320,8 +1425,9 @@ __device__ __forceinline__ void fir_poly_tile(const FirParams& p, uint32_t tile)
 #pragma unroll
     for (int r = 0; r < R; ++r) mac(acc[r], granule_sample<typename LdsSample<InT>::type>(v, r % G), 1.0f);
   } else {
-    poly_compute<TapT, InT, D, R, JC, WG, (ABL & 64) != 0>(lds, p, acc);
-    if constexpr (ABL == 0) {
+    poly_compute<TapT, InT, D, R, JC, WG, (ABL & 64) != 0, (ABL & kAblNoCarry) == 0, (ABL & kAblColumnTaps) == 0>(lds, p,
+                                                                                                                acc);
+    if constexpr ((ABL & kAblWork) == 0) {
       if (!all_finite(acc)) poly_fixup<TapT, InT, D, R, JC, WG>(lds, p, acc);
     }
   }

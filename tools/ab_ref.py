@@ -2,7 +2,8 @@
 """Side-by-side timing of the working tree's libgsdr.so against an earlier build (development tool):
     python tools/ab_ref.py build/ref_50fdf7b/libgsdr.so
 Each entry point on its bench shape, both libraries interleaved over ROUNDS rounds in one process on the same
-buffers (HIP events around back-to-back launches; min over rounds), so box-to-box spread cancels. Inputs and outputs
+buffers (HIP events around back-to-back launches; min, median and max over rounds: max - min is an arm's
+round-to-round spread), so box-to-box spread cancels. Inputs and outputs
 rotate over 3 buffer sets, as bench.py's do, so no launch re-reads or re-writes a buffer the Infinity Cache holds."""
 import ctypes
 import os
@@ -149,7 +150,7 @@ def main():
                 torch.cuda.synchronize()
                 res.setdefault((name, li), []).append(e0.elapsed_time(e1) / REPS * 1e3)
     names = [os.path.relpath(x, ROOT) for x in libs]
-    print(f"{'entry point':26s} " + " ".join(f"{n[:24]:>24s}" for n in names) + "   (min / median us)")
+    print(f"{'entry point':26s} " + " ".join(f"{n[:34]:>34s}" for n in names) + "   (min / median / max us)")
     for name in cases:
         if (name, 0) not in res:
             continue
@@ -159,8 +160,11 @@ def main():
                 cols.append("-")
                 continue
             v = sorted(res[(name, li)])
-            cols.append(f"{v[0]:11.2f} / {v[len(v) // 2]:9.2f}")
-        print(f"{name:26s} " + " ".join(f"{c:>24s}" for c in cols), flush=True)
+            cols.append(f"{v[0]:11.2f} / {v[len(v) // 2]:9.2f} / {v[-1]:9.2f}")
+        print(f"{name:26s} " + " ".join(f"{c:>34s}" for c in cols), flush=True)
+        if os.environ.get("ROUNDS_OUT") == "1":  # every round's figure, in the order measured
+            for li in range(len(L)):
+                print(f"  {names[li]}: " + " ".join(f"{t:.2f}" for t in res.get((name, li), [])), flush=True)
 
 
 if __name__ == "__main__":
