@@ -132,6 +132,23 @@ hipError_t launch_fc_probe(const FirJob& j, hipStream_t s) {
     case 153:
       return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblNoCarry | kAblColumnTaps | kAblPlainRows, true>(
           j, s);
+    // Round-8 pieces of the default kernel taken out one at a time (results unchanged):
+    // 160 the wave-owned staging of whole tiles, 161 the odd taps read from their SGPR pair, 162 the carried rows read
+    // where the old ones die, 163 all three (the kernel as it was before them). 164 (wrong results) prices the staging
+    // barrier: 160 without it.
+    case 160:
+      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblBlockStage, true>(j, s);
+    case 161:
+      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblTapMoves, true>(j, s);
+    case 162:
+      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblCarryCopies, true>(j, s);
+    case 163:
+      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblBlockStage | kAblTapMoves | kAblCarryCopies, true>(
+          j, s);
+    case 164:
+      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblBlockStage | kAblNoBarrier, true>(j, s);
+    case 165:  // the wave-owned staging with its following granules streamed (non-temporal) like the body
+      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblFollowStream, true>(j, s);
     case 110:
     case 111:
       return launch_stream_probe(j, s, j.variant == 111);

@@ -181,6 +181,7 @@ __device__ __forceinline__ float2 tap_at<float2>(const TapBuf& tb, int i) {
 // for a tap is always a full drain of that counter: with the taps settled up front, every later wait of the chunk
 // is a counted one on the in-order LDS reads alone.
 typedef float gsdr_f32x16 __attribute__((ext_vector_type(16)));
+typedef float gsdr_f32x2 __attribute__((ext_vector_type(2)));
 __device__ gsdr_f32x16 gsdr_s_buffer_load_f32x16(gsdr_v4i32 rsrc, int offset, int aux) __asm(
     "llvm.amdgcn.s.buffer.load.v16f32");
 
@@ -204,6 +205,16 @@ struct TapChunk {
     } else {
       return make_float2(q[(2 * i) / 16][(2 * i) % 16], q[(2 * i + 1) / 16][(2 * i + 1) % 16]);
     }
+  }
+  // Real taps `i` (even) and `i + 1` as the even-aligned SGPR pair they were loaded into. v_pk_fma_f32 broadcasts
+  // either half of a 64-bit scalar operand (op_sel / op_sel_hi), and the compiler selects the high half when the tap is
+  // element 1 of a two-element vector; read as element 2k + 1 of the sixteen it copied every odd tap to an even SGPR
+  // first (s_mov_b32, one per odd tap and use). The empty asm (no instruction, not volatile, the pair its only operand)
+  // keeps the pair a value of its own, so the element-of-sixteen form is not folded back in.
+  __device__ __forceinline__ gsdr_f32x2 pair(int i) const {
+    gsdr_f32x2 t = {q[i / 16][i % 16], q[i / 16][i % 16 + 1]};
+    asm("" : "+s"(t));
+    return t;
   }
 };
 // dwords of a chunk of `taps` taps, and whether it is fetched whole (1, 2 or 4 x16 loads: up to 64 SGPRs)
@@ -274,7 +285,6 @@ __device__ __forceinline__ float2 nco_direct(uint32_t phase) {
 // packed F32 -- which saves that instruction for every product whose b varies, e.g. each staged granule's NCO mix.
 // An isolated check agreed bit for bit on 2^22 products, but inside the chain kernels the results were wrong (109
 // GPU tests failed), so it is not used.)
-typedef float gsdr_f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
   const gsdr_f32x2 bv = gsdr_f32x2{b.x, b.y};
   // (-b.y, b.x) as b swapped times (-1, 1) (exact): one v_pk_mul_f32, where building it with a sign flip
@@ -917,6 +927,53 @@ __device__ __forceinline__ void stage_tile(float4* __restrict__ lds, const InT* 
   stage_halo(halo.g + WG);
 }
 
+// Wave-owned staging of a whole, aligned, unmixed tile of 16-byte quads (FIR mode; every tile of a long call but the
+// last). stage_tile's map hands thread tid the granules k WG + tid, so every wave loads a share of every body row and
+// no wave may read the tile before the slowest wave's last load has landed: a workgroup barrier. But wave w reads only
+// the segments of its own 64 threads and the tap span after them -- tile granules [w B, w B + B + H), B = 64 SG its
+// body share, H = NG - WG SG the tile's halo length. Here it stages exactly those, into the slots stage_tile would put
+// them in: SG row-base loads a lane for its body share (load_rows on the wave's base) and one predicated load for the
+// H granules that follow, issued with them, so that all arrive in one round trip. For the last wave those H are the
+// tile's halo; for the others they are also the head of wave w + 1's body share, and both waves write them, the same
+// bits to the same slots. A wave reads a slot only after its own write to it (wave_staged), so it never depends on its
+// neighbour, and a neighbour's write under a read changes nothing. Private copies would need LDS for H more granules
+// a wave, and the tile's size sets the occupancy. The following granules are read again soon after -- by the next wave,
+// or as the next tile's body -- so theirs is a plain load, as the halo's always was, while the body's loads stream
+// (NT); FNT (tuning probe) streams it too.
+// Returns false, with nothing issued, where this does not apply (uniform over the workgroup): a history tile, a tile
+// that is not wholly readable, a tap span longer than one load a lane. The caller then stages with stage_tile.
+template <class Geo, int WG, bool NT, bool FNT = false>
+__device__ __forceinline__ bool stage_tile_wave(float4* __restrict__ lds, const float2* __restrict__ in, uint64_t S0,
+                                                uint32_t NG, const FirParams& p) {
+  constexpr int SG = Geo::SG, B = 64 * SG;
+  static_assert(Geo::G == 2 && WG % 64 == 0 && 64 % SG == 0, "whole segments per wave row");
+  if (p.hist != nullptr && (int64_t)S0 + p.in_off < 0) return false;
+  if ((int64_t)S0 < 0 || S0 + (uint64_t)NG * Geo::G > p.L) return false;
+  const uint32_t H = NG - (uint32_t)(WG * SG);
+  if (H > 64u) return false;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const float4* __restrict__ wb = reinterpret_cast<const float4*>(in + S0) + w * B;  // wave-uniform
+  float4 v[SG];
+  load_rows<SG, 64, NT>(v, wb, 0, lane);
+  const bool follow = lane < H;
+  float4 f[1];  // (left indeterminate where nothing is loaded, as HaloPre::raw)
+  if (follow) load_rows<1, 64, FNT>(f, wb + B, 0, lane);
+  float4* __restrict__ dst = lds + w * (64 * Geo::SGP) + Geo::padded(lane);
+#pragma unroll
+  for (int k = 0; k < SG; ++k) dst[k * (64 / SG) * Geo::SGP] = v[k];
+  if (follow) dst[64 * Geo::SGP] = f[0];
+  return true;
+}
+
+// The wave's own wait behind stage_tile_wave: its LDS writes are done, and no LDS read is moved above this point.
+__device__ __forceinline__ void wave_staged() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // ------------------------------------------------------------------------------------------------
 // Epilogues
 // ------------------------------------------------------------------------------------------------
@@ -1161,6 +1218,15 @@ __device__ __forceinline__ void tile_epilogue(const FirParams& p, uint64_t out0,
   }
 }
 
+// An ordering point (no instruction): memory accesses written after it stay after the products accumulated into `a`
+// so far.
+__device__ __forceinline__ void after_products(float& a) { asm volatile("" : "+v"(a)::"memory"); }
+__device__ __forceinline__ void after_products(float2& a) {
+  gsdr_f32x2 v = {a.x, a.y};
+  asm volatile("" : "+v"(v)::"memory");
+  a = make_float2(v.x, v.y);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Polyphase compute core shared by the polyphase kernels: thread t accumulates its R outputs from
 // the staged tile in LDS. JC = tap rows per chunk (a multiple of R); a chunk covers JC*D taps.
@@ -1172,8 +1238,11 @@ __device__ __forceinline__ void tile_epilogue(const FirParams& p, uint64_t out0,
 //     saved in every chunk but the first. The first chunk is peeled, so which reads exist is fixed at compile time.
 //   The order of every accumulator's products (chunk c, column h, row j, element e) is untouched by either.
 // CARRY / BATCH = false (tuning probes): the core without the carried rows / with per-column tap batches.
+// PAIRS / LATE = false (tuning probes): odd taps copied out of their pair / the carried rows read with the rest of the
+// window and copied.
 // ------------------------------------------------------------------------------------------------
-template <class TapT, class InT, int D, int R, int JC, int WG, bool LIGHT = false, bool CARRY = true, bool BATCH = true>
+template <class TapT, class InT, int D, int R, int JC, int WG, bool LIGHT = false, bool CARRY = true, bool BATCH = true,
+          bool PAIRS = true, bool LATE = true>
 __device__ __forceinline__ void poly_compute(const float4* __restrict__ lds, const FirParams& p,
                                              typename Product<TapT, InT>::type (&acc)[R]) {
   using Geo = TileGeo<InT, D, R, WG>;
@@ -1185,6 +1254,13 @@ __device__ __forceinline__ void poly_compute(const float4* __restrict__ lds, con
   constexpr int NCARRY = (CARRY && !LIGHT) ? R - 1 : 0;  // (JC >= R: the carried rows are the chunk's own reads)
   constexpr int CHUNK_DW = tap_chunk_dwords<TapT>(JC * D);
   constexpr bool WHOLE = BATCH && tap_chunk_whole(CHUNK_DW);
+  // real taps against complex samples: a granule's two taps are one even-aligned SGPR pair (TapChunk::pair)
+  constexpr bool PAIRED = PAIRS && WHOLE && std::is_same<TapT, float>::value && G == 2 && D % 2 == 0;
+  // the rows carried to the next chunk are read where the carried rows of this one die (below)
+  constexpr int NLATE = (LATE && NCARRY > 0 && JC > 2 * NCARRY) ? NCARRY : 0;
+  // (tap row of that point: 3 tap rows, 12 R FMAs, ahead of the new rows' first product; no earlier than the old rows'
+  // last)
+  constexpr int LATE_J = (JC - NCARRY - 3) > NCARRY ? (JC - NCARRY - 3) : NCARRY;
   const uint32_t t = threadIdx.x;
   float4 carry[CPR][NCARRY > 0 ? NCARRY : 1];
   auto chunk = [&](uint32_t c, auto first) __attribute__((always_inline)) {
@@ -1198,7 +1274,14 @@ __device__ __forceinline__ void poly_compute(const float4* __restrict__ lds, con
 #pragma unroll
     for (int h = 0; h < CPR; ++h) {
       TapT tv[JC][G];
-      if constexpr (WHOLE) {
+      if constexpr (PAIRED) {
+#pragma unroll
+        for (int j = 0; j < JC; ++j) {
+          const gsdr_f32x2 tp = tc.pair(j * D + h * G);
+          tv[j][0] = tp.x;
+          tv[j][1] = tp.y;
+        }
+      } else if constexpr (WHOLE) {
 #pragma unroll
         for (int j = 0; j < JC; ++j) {
 #pragma unroll
@@ -1213,9 +1296,12 @@ __device__ __forceinline__ void poly_compute(const float4* __restrict__ lds, con
         }
       }
       float4 win[NWIN];
-#pragma unroll
-      for (int u = 0; u < NWIN; ++u) {
+      auto read_row = [&](int u) __attribute__((always_inline)) {
         const int q = u * CPR + h;
+        return seg[q + Geo::PAD * (q / Geo::SG)];
+      };
+#pragma unroll
+      for (int u = 0; u < NWIN - NLATE; ++u) {
         // LIGHT (tuning probe, wrong results): only the thread's own R rows come from LDS, the rest of
         // the window repeats them -- the same FMAs with 4/19 of the LDS reads
         if (LIGHT && u >= R) {
@@ -1223,13 +1309,28 @@ __device__ __forceinline__ void poly_compute(const float4* __restrict__ lds, con
         } else if (!FIRST && u < NCARRY) {
           win[u] = carry[h][u];
         } else {
-          win[u] = seg[q + Geo::PAD * (q / Geo::SG)];
+          win[u] = read_row(u);
         }
       }
+      if constexpr (NLATE == 0) {
 #pragma unroll
-      for (int u = 0; u < NCARRY; ++u) carry[h][u] = win[JC + u];
+        for (int u = 0; u < NCARRY; ++u) carry[h][u] = win[JC + u];
+      }
 #pragma unroll
       for (int j = 0; j < JC; ++j) {
+        // Rows JC .. JC + NCARRY - 1 become the next chunk's rows 0 .. NCARRY - 1. The old rows' last products are
+        // tap row j = NCARRY - 1's (into acc[0 .. NCARRY - 1]) and the new rows' first are tap row j = JC - NCARRY's,
+        // so read at this point the new rows never live beside the old ones and take their registers: read with the
+        // rest of the window, they were copied into them (v_mov_b64, 2 a carried granule and chunk). after_products
+        // keeps the reads behind those products while registers are assigned.
+        if constexpr (NLATE > 0) {
+          if (j == LATE_J) {
+#pragma unroll
+            for (int u = 0; u < NCARRY; ++u) after_products(acc[u]);
+#pragma unroll
+            for (int u = 0; u < NCARRY; ++u) win[JC + u] = carry[h][u] = read_row(JC + u);
+          }
+        }
 #pragma unroll
         for (int e = 0; e < G; ++e) {
 #pragma unroll
@@ -1362,6 +1463,12 @@ __device__ __forceinline__ bool all_finite(const float (&acc)[R]) {
 // ------------------------------------------------------------------------------------------------
 constexpr int kAblWork = 127;  // the flags that change what the kernel computes
 constexpr int kAblNoCarry = 128, kAblColumnTaps = 256, kAblPlainRows = 512;
+// The same for the round-8 pieces: 1024 = every tile staged by the workgroup's map behind the workgroup barrier,
+// 2048 = odd taps copied out of their SGPR pair, 4096 = carried rows read with the window and copied. 8192 (wrong
+// results: a probe of what the barrier costs) = the workgroup's map with no barrier behind it. 16384 = the wave-owned
+// staging with its following granules loaded non-temporally too.
+constexpr int kAblBlockStage = 1024, kAblTapMoves = 2048, kAblCarryCopies = 4096, kAblNoBarrier = 8192;
+constexpr int kAblFollowStream = 16384;
 
 // Tile of workgroup b. XCD-aware (XM): workgroups are dispatched round-robin over the 8 XCDs, so
 // with the identity map neighbouring tiles (which share a halo of input rows) sit on different L2s;
@@ -1405,15 +1512,27 @@ __device__ __forceinline__ void fir_poly_tile(const FirParams& p, uint32_t tile)
   // the tile is sub-tile `sub` of its NCO cell: it starts sub (KT - R) outputs (FM) or sub KT outputs (AM, IQ) into
   // the cell, i.e. sub BPT granule rows in, less sub SG granules for FM (MixAnchored)
   const uint32_t sub = ANCH ? (p.cell_sub0 + tile) % SUBS : 0u;
+  // Whole tiles of the full-size FIR tile on aligned complex samples are staged wave by wave, with the wave's own
+  // wait behind them (stage_tile_wave; uniform over the workgroup). Everything else -- the chains, the shifted and DMA
+  // staging, the tile stores through LDS, smaller workgroups, and the tiles that path declines -- keeps the workgroup's
+  // map and its barrier.
+  constexpr bool WAVE = MODE == kModeFir && std::is_same<InT, float2>::value && VEC && SH == 0 && !DMA && CST == 0 &&
+                        WG == 256 && 64 % Geo::SG == 0 && (ABL & (7 | kAblPlainRows | kAblBlockStage)) == 0;
+  bool waved = false;
   if constexpr ((ABL & 7) != 2) {
     if constexpr (ANCH && (ABL & 8) == 0) {
       stage_tile<InT, Geo, WG, VEC, NT, DMA, SH, (ABL & kAblPlainRows) == 0>(
           lds, in, S0, NG, p, MixAnchored<WG>(p.nco_inc, sub * BPT, MODE == kModeFm ? sub * Geo::SG : 0u));
     } else {
-      stage_tile<InT, Geo, WG, VEC, NT, DMA, SH, (ABL & kAblPlainRows) == 0>(lds, in, S0, NG, p, MixNone{});
+      if constexpr (WAVE) waved = stage_tile_wave<Geo, WG, NT, NT && (ABL & kAblFollowStream) != 0>(lds, in, S0, NG, p);
+      if (!waved) stage_tile<InT, Geo, WG, VEC, NT, DMA, SH, (ABL & kAblPlainRows) == 0>(lds, in, S0, NG, p, MixNone{});
     }
   }
-  __syncthreads();
+  if (waved) {
+    wave_staged();
+  } else if constexpr ((ABL & kAblNoBarrier) == 0) {
+    __syncthreads();
+  }
   stream_history_store<InT>(p, hist);
   float2* xs = reinterpret_cast<float2*>(lds + Geo::padded(NG - 1) + 1);
 
@@ -1425,8 +1544,9 @@ __device__ __forceinline__ void fir_poly_tile(const FirParams& p, uint32_t tile)
 #pragma unroll
     for (int r = 0; r < R; ++r) mac(acc[r], granule_sample<typename LdsSample<InT>::type>(v, r % G), 1.0f);
   } else {
-    poly_compute<TapT, InT, D, R, JC, WG, (ABL & 64) != 0, (ABL & kAblNoCarry) == 0, (ABL & kAblColumnTaps) == 0>(lds, p,
-                                                                                                                acc);
+    poly_compute<TapT, InT, D, R, JC, WG, (ABL & 64) != 0, (ABL & kAblNoCarry) == 0, (ABL & kAblColumnTaps) == 0,
+                 MODE == kModeFir && (ABL & kAblTapMoves) == 0, MODE == kModeFir && (ABL & kAblCarryCopies) == 0>(lds, p,
+                                                                                                                   acc);
     if constexpr ((ABL & kAblWork) == 0) {
       if (!all_finite(acc)) poly_fixup<TapT, InT, D, R, JC, WG>(lds, p, acc);
     }

@@ -2,7 +2,7 @@
 """Headline-shape FIR tile variants (gsdrxFirFCVariant) timed side by side with inputs AND outputs rotating over 3
 buffer sets (bench.py's timed region since round 6), and each also on one fixed output buffer (development tool):
     python tools/fir_variants_rotated.py [variant ...]      (default 0 8 10 11 14)
-Interleaved over ROUNDS rounds in one process; min / median us per launch."""
+Interleaved over ROUNDS rounds in one process; min / median / max us per launch (max - min: the variant's spread)."""
 import ctypes
 import os
 import sys
@@ -49,8 +49,8 @@ def main():
         cols = []
         for mode in ("rotated", "one_output"):
             t = sorted(res[(v, mode)])
-            cols.append(f"{mode} {t[0]:7.2f} / {t[len(t) // 2]:7.2f}")
-        print(f"variant {v:3d}   " + "   ".join(cols) + "   us (min / median)", flush=True)
+            cols.append(f"{mode} {t[0]:7.2f} / {t[len(t) // 2]:7.2f} / {t[-1]:7.2f}")
+        print(f"variant {v:3d}   " + "   ".join(cols) + "   us (min / median / max)", flush=True)
 
 
 if __name__ == "__main__":
