@@ -9,7 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "channelizer_plan.hpp"
-#include "fir_engine.hpp"
+#include "fir_samples.hpp"
 #include "gsdr/gsdr_ext.h"
 #include "launch.hpp"
 

@@ -43,112 +43,61 @@ __global__ __launch_bounds__(256) void k_stream_probe(const float4* __restrict__
 hipError_t launch_stream_probe(const FirJob& j, hipStream_t s, bool nt) {
   const uint64_t n_in16 = j.L * 8 / 16, n_out16 = j.N * 8 / 16;
   const uint32_t blocks = (uint32_t)ceil_div<uint64_t>(n_out16, 256);
-  if (nt) {
-    k_stream_probe<true><<<blocks, 256, 0, s>>>(reinterpret_cast<const float4*>(j.in),
-                                                reinterpret_cast<float4*>(j.out), n_in16, n_out16);
-  } else {
-    k_stream_probe<false><<<blocks, 256, 0, s>>>(reinterpret_cast<const float4*>(j.in),
-                                                 reinterpret_cast<float4*>(j.out), n_in16, n_out16);
-  }
+  const auto k = nt ? k_stream_probe<true> : k_stream_probe<false>;
+  k<<<blocks, 256, 0, s>>>(reinterpret_cast<const float4*>(j.in), reinterpret_cast<float4*>(j.out), n_in16, n_out16);
   return launch_status();
+}
+
+// The headline shape (GSDR_FIR_ROWS row C4; real taps against complex samples) and the probes' launch of a tile on it.
+using Headline = TileShape<4, 4, 16, 256>;
+struct StreamedDma : TileStreamed {  // variant 14's options
+  static constexpr bool DMA = true;
+};
+struct StreamedXcdOrder : TileStreamed {  // variant 9's options
+  static constexpr bool XM = true;
+};
+template <int MODE, class Opts, class Shape = Headline>
+hipError_t launch_probe(const FirJob& j, hipStream_t s) {
+  return launch_poly_shape<float, float2, Shape, MODE, Opts>(j, s);
 }
 
 // Ablation probes (gsdrxFirFCVariant >= 100) used for the energy split in DESIGN.md section 3.1:
 // the default shape with only one half of its work.
 hipError_t launch_fc_probe(const FirJob& j, hipStream_t s) {
+  // the FM chain (config 3's shape) on the same buffers, for the probes from 120 on
+  FirJob c = j;
+  c.mode = kModeFm;
+  c.N = j.N - 1;  // an FM output needs one more FIR output than the input holds for N FIR outputs
+  c.nco_inc = 429496730u;  // 0.1 fs
+  c.fm_gain = 7.957747f;   // fs / (2 pi 0.02 fs)
   switch (j.variant) {
     case 104:  // compute only (no staging; the tile holds whatever LDS held)
-      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, 2, true>(j, s);
+      return launch_probe<kModeFir, Probed<TileStreamed, kProbeComputeOnly>>(j, s);
     case 105:  // staging only, plain loads
-      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, 1>(j, s);
+      return launch_probe<kModeFir, Probed<TileOpts<>, kProbeStageOnly>>(j, s);
     case 107:  // staging only, non-temporal loads
-      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, 1, true>(j, s);
+      return launch_probe<kModeFir, Probed<TileStreamed, kProbeStageOnly>>(j, s);
     case 113:  // matrix-core kernel with register taps, compute only
-      return launch_mfma_bc_shape<2>(j, s);
+      return launch_mfma_bc_shape<kProbeComputeOnly>(j, s);
     case 117:  // staging only by LDS-DMA, non-temporal
-      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, 1, true, false, 0, true>(j, s);
-    // FM chain (config 3 shape) split: 120 full FM kernel, 121 no NCO mix, 122 no discriminator (plain
-    // float store), 123 neither, 124 staging + NCO + discriminator without the FIR, 125 staging only
-    case 120:
-    case 121:
-    case 122:
-    case 123:
-    case 124:
-    case 125: {
-      FirJob c = j;
-      c.mode = kModeFm;
-      c.N = j.N - 1;  // an FM output needs one more FIR output than the input holds for N FIR outputs
-      c.nco_inc = 429496730u;  // 0.1 fs
-      c.fm_gain = 7.957747f;   // fs / (2 pi 0.02 fs)
-      switch (j.variant) {
-        case 120: return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFm, 0, true>(c, s);
-        case 121: return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFm, 8, true>(c, s);
-        case 122: return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFm, 16, true>(c, s);
-        case 123: return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFm, 24, true>(c, s);
-        case 124: return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFm, 1, true>(c, s);
-        default: return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFm, 25, true>(c, s);
-      }
-    }
-    // FM chain (config 3 shape) tile-shape sweep: 130 default (R 4, JC 16, WG 256), 131 R 8 WG 128,
-    // 132 JC 8, 133 R 2, 134 WG 128, 135 R 8 JC 8 WG 128, 136 default with the XCD-aware tile order
-    case 130:
-    case 131:
-    case 132:
-    case 133:
-    case 134:
-    case 135:
-    case 136: {
-      FirJob c = j;
-      c.mode = kModeFm;
-      c.N = j.N - 1;
-      c.nco_inc = 429496730u;  // 0.1 fs
-      c.fm_gain = 7.957747f;   // fs / (2 pi 0.02 fs)
-      switch (j.variant) {
-        case 130: return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFm, 0, true>(c, s);
-        case 131: return launch_poly_shape<float, float2, 4, 8, 16, 128, kModeFm, 0, true>(c, s);
-        case 132: return launch_poly_shape<float, float2, 4, 4, 8, 256, kModeFm, 0, true>(c, s);
-        case 133: return launch_poly_shape<float, float2, 4, 2, 16, 256, kModeFm, 0, true>(c, s);
-        case 134: return launch_poly_shape<float, float2, 4, 4, 16, 128, kModeFm, 0, true>(c, s);
-        case 135: return launch_poly_shape<float, float2, 4, 8, 8, 128, kModeFm, 0, true>(c, s);
-        default: return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFm, 0, true, true>(c, s);
-      }
-    }
-    // LDS-read probe: the default kernel with the register window served from the
-    // thread's own R rows only (4 of 19 ds_read_b128 per column and chunk; wrong results, same FMAs):
-    // 140 full kernel, 141 compute only
-    case 140:
-      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, 64, true>(j, s);
-    case 141:
-      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, 66, true>(j, s);
-    // Round-7 pieces of the default kernel taken out one at a time (results unchanged):
-    // 150 the carried window rows, 151 the whole-chunk tap batch, 152 the row-base staging loads, 153 all three
-    // (the kernel as it was before them)
-    case 150:
-      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblNoCarry, true>(j, s);
-    case 151:
-      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblColumnTaps, true>(j, s);
-    case 152:
-      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblPlainRows, true>(j, s);
-    case 153:
-      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblNoCarry | kAblColumnTaps | kAblPlainRows, true>(
-          j, s);
-    // Round-8 pieces of the default kernel taken out one at a time (results unchanged):
-    // 160 the wave-owned staging of whole tiles, 161 the odd taps read from their SGPR pair, 162 the carried rows read
-    // where the old ones die, 163 all three (the kernel as it was before them). 164 (wrong results) prices the staging
-    // barrier: 160 without it.
-    case 160:
-      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblBlockStage, true>(j, s);
-    case 161:
-      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblTapMoves, true>(j, s);
-    case 162:
-      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblCarryCopies, true>(j, s);
-    case 163:
-      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblBlockStage | kAblTapMoves | kAblCarryCopies, true>(
-          j, s);
-    case 164:
-      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblBlockStage | kAblNoBarrier, true>(j, s);
-    case 165:  // the wave-owned staging with its following granules streamed (non-temporal) like the body
-      return launch_poly_shape<float, float2, 4, 4, 16, 256, kModeFir, kAblFollowStream, true>(j, s);
+      return launch_probe<kModeFir, Probed<StreamedDma, kProbeStageOnly>>(j, s);
+    // FM chain split: 120 full FM kernel, 121 no NCO mix, 122 no discriminator (plain float store), 123 neither,
+    // 124 staging + NCO + discriminator without the FIR, 125 staging only
+    case 120: return launch_probe<kModeFm, TileStreamed>(c, s);
+    case 121: return launch_probe<kModeFm, Probed<TileStreamed, kProbeNoMix>>(c, s);
+    case 122: return launch_probe<kModeFm, Probed<TileStreamed, kProbeNoDisc>>(c, s);
+    case 123: return launch_probe<kModeFm, Probed<TileStreamed, kProbeNoMix | kProbeNoDisc>>(c, s);
+    case 124: return launch_probe<kModeFm, Probed<TileStreamed, kProbeStageOnly>>(c, s);
+    case 125: return launch_probe<kModeFm, Probed<TileStreamed, kProbeStageOnly | kProbeNoMix | kProbeNoDisc>>(c, s);
+    // FM chain tile-shape sweep: 130 default (R 4, JC 16, WG 256), 131 R 8 WG 128, 132 JC 8, 133 R 2, 134 WG 128,
+    // 135 R 8 JC 8 WG 128, 136 default with the XCD-aware tile order
+    case 130: return launch_probe<kModeFm, TileStreamed>(c, s);
+    case 131: return launch_probe<kModeFm, TileStreamed, TileShape<4, 8, 16, 128>>(c, s);
+    case 132: return launch_probe<kModeFm, TileStreamed, TileShape<4, 4, 8, 256>>(c, s);
+    case 133: return launch_probe<kModeFm, TileStreamed, TileShape<4, 2, 16, 256>>(c, s);
+    case 134: return launch_probe<kModeFm, TileStreamed, TileShape<4, 4, 16, 128>>(c, s);
+    case 135: return launch_probe<kModeFm, TileStreamed, TileShape<4, 8, 8, 128>>(c, s);
+    case 136: return launch_probe<kModeFm, StreamedXcdOrder>(c, s);
     case 110:
     case 111:
       return launch_stream_probe(j, s, j.variant == 111);

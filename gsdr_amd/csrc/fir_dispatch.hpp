@@ -29,7 +29,7 @@ struct FirJob {
   float fm_gain = 0.0f;
   uint32_t out_phase = 0;  // absolute index of output 0 mod 16 (fir_i8_mfma.hpp)
   uint64_t q0 = 0;         // chains: absolute index of output 0 (firstSampleIndex / D) -- the anchored
-                           // polyphase tiles' NCO cell grid (fir_engine.hpp, MixAnchored)
+                           // polyphase tiles' NCO cell grid (fir_nco.hpp, MixAnchored)
   // a streaming step's operands (FirParams): `in` is then the chunk and L its length. All zero otherwise.
   StreamOperands step{};
   // the streaming object's one-launch path on the tiled kernels (stream_step_tiled): only the polyphase and
@@ -155,13 +155,11 @@ hipError_t launch_generic_kernel(const firplan::Plan& pl, const FirParams& p, hi
   return launch_status();
 }
 
-template <class TapT, class InT, int D, int R, int JC, int WG, int MODE, int ABL = 0, bool NT = false, bool XM = false,
-          int CST = 0, bool DMA = false, int SUBS = 1>
+template <class TapT, class InT, class Shape, int MODE, class Opts>
 hipError_t launch_poly(const firplan::Plan& pl, const FirParams& p, hipStream_t s) {
   with_staging<InT>(pl, [&](auto vec, auto sh) {
-    constexpr int SH = decltype(sh)::value;  // the shifted loads have no LDS-DMA form
-    k_fir_poly<TapT, InT, D, R, JC, WG, decltype(vec)::value, MODE, ABL, NT, XM, CST, (SH == 0 && DMA), SH, SUBS>
-        <<<dim3(pl.grid), dim3(WG), pl.lds, s>>>(p);
+    k_fir_poly<TapT, InT, Shape, decltype(vec)::value, MODE, decltype(sh)::value, Opts>
+        <<<dim3(pl.grid), dim3(Shape::WG), pl.lds, s>>>(p);
   });
   return launch_status();
 }
@@ -178,12 +176,12 @@ hipError_t launch_contig(const firplan::Plan& pl, const FirParams& p, hipStream_
 // Multi-channel chain (k_fir_poly_grouped): one launch per group of <= kMaxMultiChannels channels, the single-channel
 // polyphase tile with the C channels of an input tile grouped on one XCD (same staging choice as launch_poly, so each
 // channel is that kernel's call bit for bit).
-template <class TapT, class InT, int D, int R, int JC, int WG, int MODE>
+template <class TapT, class InT, class Shape, int MODE>
 hipError_t launch_poly_grouped(const firplan::Plan& pl, const FirParams& p, const MultiParams& mp, hipStream_t s) {
   static_assert(!std::is_same<InT, float>::value, "complex or int8 I/Q samples: one shifted form");
   with_staging<InT>(pl, [&](auto vec, auto sh) {
-    k_fir_poly_grouped<TapT, InT, D, R, JC, WG, decltype(vec)::value, MODE, decltype(sh)::value>
-        <<<dim3(pl.grid), dim3(WG), pl.lds, s>>>(p, mp, (uint32_t)pl.tiles);
+    k_fir_poly_grouped<TapT, InT, Shape, decltype(vec)::value, MODE, decltype(sh)::value>
+        <<<dim3(pl.grid), dim3(Shape::WG), pl.lds, s>>>(p, mp, (uint32_t)pl.tiles);
   });
   return launch_status();
 }
@@ -192,11 +190,8 @@ hipError_t launch_poly_grouped(const firplan::Plan& pl, const FirParams& p, cons
 template <int ABL = 0>
 hipError_t launch_mfma_bc(const firplan::Plan& pl, const FirParams& p, hipStream_t s) {
   constexpr int WG = firplan::kMfmaBcWG, MAXSEG = firplan::kMfmaBcMaxSeg;
-  if (pl.vec) {
-    k_fir_mfma_bc<WG, MAXSEG, true, true, ABL><<<dim3(pl.grid), dim3(WG), pl.lds, s>>>(p);
-  } else {
-    k_fir_mfma_bc<WG, MAXSEG, false, true, ABL><<<dim3(pl.grid), dim3(WG), pl.lds, s>>>(p);
-  }
+  const auto k = pl.vec ? k_fir_mfma_bc<WG, MAXSEG, true, true, ABL> : k_fir_mfma_bc<WG, MAXSEG, false, true, ABL>;
+  k<<<dim3(pl.grid), dim3(WG), pl.lds, s>>>(p);
   return launch_status();
 }
 
@@ -240,7 +235,7 @@ hipError_t launch_row(const firplan::Plan& pl, const FirParams& p, hipStream_t s
   case kRow##NAME:                                                                                          \
     if constexpr (row_serves(CLS, TAPS, SampleKind<InT>::value, kTapKind)) {                                \
       if constexpr (KERN == kPoly) {                                                                        \
-        return launch_poly<TapT, InT, D, R, CH, WG, MODE, 0, true, false, 0, false, SUBS>(pl, p, s);       \
+        return launch_poly<TapT, InT, TileShape<D, R, CH, WG, SUBS>, MODE, TileStreamed>(pl, p, s);         \
       } else {                                                                                              \
         return launch_contig<TapT, InT, D, R, CH, WG, MODE>(pl, p, s);                                      \
       }                                                                                                     \
@@ -257,11 +252,11 @@ hipError_t launch_row(const firplan::Plan& pl, const FirParams& p, hipStream_t s
 template <class TapT, class InT, int MODE>
 hipError_t launch_d4_variant(const firplan::Plan& pl, const FirParams& p, hipStream_t s) {
   switch (pl.variant) {
-#define GSDR_FIR_LAUNCH_VARIANT(V, I8, R, JC, WG, NT, XM, CST, DMA)                                   \
-  case V:                                                                                             \
-    if constexpr (I8 != 0 || !std::is_same<InT, Iq8>::value) {                                        \
-      return launch_poly<TapT, InT, 4, R, JC, WG, MODE, 0, NT != 0, XM != 0, CST, DMA != 0>(pl, p, s); \
-    }                                                                                                 \
+#define GSDR_FIR_LAUNCH_VARIANT(V, I8, R, JC, WG, NT, XM, CST, DMA)                                                     \
+  case V:                                                                                                               \
+    if constexpr (I8 != 0 || !std::is_same<InT, Iq8>::value) {                                                          \
+      return launch_poly<TapT, InT, TileShape<4, R, JC, WG>, MODE, TileOpts<NT != 0, XM != 0, CST, DMA != 0>>(pl, p, s); \
+    }                                                                                                                   \
     break;
     GSDR_FIR_D4_VARIANTS(GSDR_FIR_LAUNCH_VARIANT)
 #undef GSDR_FIR_LAUNCH_VARIANT
@@ -329,15 +324,15 @@ hipError_t launch_generic(const FirJob& j, hipStream_t s) {
 
 // An explicit tile shape (the probes): the plan's tile arithmetic for it, then the kernel. A tap span that does not
 // fit runs the generic kernel, as for a row.
-template <class TapT, class InT, int D, int R, int JC, int WG, int MODE, int ABL = 0, bool NT = false, bool XM = false,
-          int CST = 0, bool DMA = false>
+template <class TapT, class InT, class Shape, int MODE, class Opts>
 hipError_t launch_poly_shape(const FirJob& j, hipStream_t s) {
-  const firplan::Row shape{SampleT<InT>::kPerGranule, firplan::kTapsAny, D, firplan::kPoly, R, JC, WG, 1, 0};
+  const firplan::Row shape{SampleT<InT>::kPerGranule, firplan::kTapsAny, Shape::D, firplan::kPoly, Shape::R, Shape::JC,
+                           Shape::WG, 1, 0};
   const firplan::Plan pl = firplan::plan_shape(describe<TapT, InT>(j, MODE), shape);
   if (pl.status != firplan::kOk) return plan_status(pl, hipSuccess);
   const FirParams p = make_params(j, pl);
   if (pl.family == firplan::kFamGeneric) return launch_generic_kernel<TapT, InT, MODE>(pl, p, s);
-  return launch_poly<TapT, InT, D, R, JC, WG, MODE, ABL, NT, XM, CST, DMA>(pl, p, s);
+  return launch_poly<TapT, InT, Shape, MODE, Opts>(pl, p, s);
 }
 template <int ABL>
 hipError_t launch_mfma_bc_shape(const FirJob& j, hipStream_t s) {
@@ -359,7 +354,7 @@ hipError_t launch_multi_chain(const FirJob& j, const MultiParams& mp, hipStream_
 #define GSDR_FIR_LAUNCH_MULTI(NAME, CLS, TAPS, D, KERN, R, CH, WG, SUBS, ROLE)        \
   case kRow##NAME:                                                                    \
     if constexpr (((ROLE) & kMulti) != 0 && CLS == SampleT<InT>::kPerGranule) {       \
-      return launch_poly_grouped<float, InT, D, R, CH, WG, MODE>(pl, p, mp, s);       \
+      return launch_poly_grouped<float, InT, TileShape<D, R, CH, WG>, MODE>(pl, p, mp, s); \
     }                                                                                 \
     break;
     GSDR_FIR_ROWS(GSDR_FIR_LAUNCH_MULTI)

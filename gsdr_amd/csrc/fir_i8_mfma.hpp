@@ -488,7 +488,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BPC, BPC)))
 
 // ------------------------------------------------------------------------------------------------
 // int8 I/Q FM / AM chains on the matrix cores (gsdrxFmDemodInt8 / gsdrxAmDemodInt8, D = 4, T <= 132).
-// The NCO moves into the taps: with phi(n) the mixer phase of sample n (exact integer phase, fir_engine.hpp),
+// The NCO moves into the taps: with phi(n) the mixer phase of sample n (exact integer phase, fir_nco.hpp),
 //   y[k] = sum_i t_i x[4k+i] e^{j phi(4k+i)} = e^{j phi(4k)} y'[k],  y'[k] = sum_i t'_i x[4k+i],
 //   t'_i = t_i e^{j 2 pi (i inc mod 2^32) / 2^32}
 // (the phase is additive mod 2^32). The AM envelope |y| = |y'|, and the FM discriminator

@@ -48,7 +48,7 @@ constexpr uint64_t kMaxTiledTaps = 1u << 26;     // the tiled kernels address ta
 constexpr uint64_t kMaxTapSpan = 0x40000000ull;  // padded tap span of a tile, samples
 
 // ------------------------------------------------------------------------------------------------
-// Tile geometry (TileGeo, fir_engine.hpp): a thread's segment is SG granules; when SG is even a one-granule pad
+// Tile geometry (TileGeo, fir_staging.hpp): a thread's segment is SG granules; when SG is even a one-granule pad
 // follows each segment, so the per-lane stride is odd (conflict-free ds_read_b128).
 // ------------------------------------------------------------------------------------------------
 constexpr int tile_sg(int G, int D, int R) { return R * D / G; }
@@ -349,7 +349,7 @@ inline void plan_staging(const Call& c, uint64_t tile_samples, Plan* p) {
 }
 
 // A tiled launch of an explicit shape. Polyphase tile grid, FIR: tile t = outputs [t KT, (t + 1) KT). Chains (anchored
-// NCO, fir_engine.hpp MixAnchored): tiles on an absolute output grid of stride S -- KT for AM and IQ; KT - R for FM,
+// NCO, fir_nco.hpp MixAnchored): tiles on an absolute output grid of stride S -- KT for AM and IQ; KT - R for FM,
 // whose tiles overlap by one thread's outputs so that every discriminator pairs two outputs of one tile -- output 0
 // (absolute index q0) sits at tile_shift = q0 mod S in tile 0, which is sub-tile cell_sub0 of its NCO cell of SUBS
 // tiles (CELL = SUBS S outputs). The contiguous-window tiles start at output 0 (fm_tile_stride). A tap span that does

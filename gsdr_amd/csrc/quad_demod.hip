@@ -6,7 +6,7 @@
 // writes one 16-byte store (the reference uses 32-thread blocks, one output per thread).
 #include <hip/hip_runtime.h>
 
-#include "fir_engine.hpp"
+#include "fir_demod.hpp"
 #include "gsdr/arithmetic.h"
 #include "gsdr/quad_demod.h"
 #include "launch.hpp"

@@ -14,7 +14,7 @@ namespace gsdr {
 
 // (enum Mode { kModeFir, kModeFm, kModeAm, kModeIq }: fir_plan.hpp)
 
-// One streaming step's input (FirParams, fir_engine.hpp): output 0's window starts at sample in_off of the
+// One streaming step's input (FirParams, fir_nco.hpp): output 0's window starts at sample in_off of the
 // chunk (negative: in the history `hist` of hist_len samples, chunk offset i < 0 being hist[hist_len + i]);
 // workgroup 0 of the launch copies chunk offsets [hist_from, hist_from + hist_n) to hist_out, the next
 // history (nullptr: no copy).

@@ -7,7 +7,7 @@
     am[m]  = 2 clip(|y[m]|, 0, 1) - 1
 
 test_nco_increment.py ties it to the project's oracle at every row of FREQS. FREQS holds the NCO increments that
-are special to this implementation (gsdr_amd/csrc/fir_engine.hpp nco_direct, stage_anchored's row factor F,
+are special to this implementation (gsdr_amd/csrc/fir_nco.hpp nco_direct, stage_anchored's row factor F,
 fir_i8_mfma.hpp's left-out rotation dphi); `inputs` builds the signals both test files feed the chains."""
 from fractions import Fraction
 

@@ -1,6 +1,7 @@
 """The headline FIR tile (real taps, complex samples, D = 4: R 4, chunk 16, WG 256) stages whole tiles wave by wave,
 with the wave's own wait where the workgroup barrier stood, reads odd taps from the high half of their SGPR pair and
-reads the carried window rows where the old ones die (fir_engine.hpp: stage_tile_wave, TapChunk::pair, poly_compute).
+reads the carried window rows where the old ones die (fir_staging.hpp: stage_tile_wave; fir_engine.hpp: TapChunk::pair,
+poly_compute).
 None of it may change a bit: every kernel with the same (D, chunk) sums the same products in the same order.
 
 Bars. Bit identity (uint64 views of the complex64 outputs) of gsdrFirFC against gsdrxFirFCVariant 28 and 24, the same

@@ -1,4 +1,4 @@
-# Development tool: fit of the odd polynomial used by disc_atan2 (gsdr_amd/csrc/fir_engine.hpp) and its
+# Development tool: fit of the odd polynomial used by disc_atan2 (gsdr_amd/csrc/fir_demod.hpp) and its
 # max abs error when evaluated in float32 (Lawson-weighted least squares toward minimax).
 import numpy as np
 # fit atan(t)/t = P(s), s = t^2, t in [0,1], weighted least squares on Chebyshev nodes, then check float32 eval
