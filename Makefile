@@ -1,6 +1,7 @@
 # gsdr-mi355x build: libgsdr.so (HIP, gfx950) and the CPU oracle (plain C, test infrastructure only).
 HIPCC   ?= /opt/rocm/bin/hipcc
 CC      ?= gcc
+PYTHON  ?= python3
 ARCH    ?= gfx950
 BUILD   := build
 
@@ -13,7 +14,7 @@ SRCS := $(wildcard gsdr_amd/csrc/*.hip)
 HDRS := $(wildcard gsdr_amd/csrc/*.hpp) $(wildcard gsdr_amd/csrc/*.inc) $(wildcard include/gsdr/*.h)
 OBJS := $(patsubst gsdr_amd/csrc/%.hip,$(BUILD)/%.o,$(SRCS))
 
-all: gsdr_amd/libgsdr.so oracle/build/liboracle.so examples probes
+all: gsdr_amd/libgsdr.so oracle/build/liboracle.so examples probes refhost
 
 $(BUILD)/%.o: gsdr_amd/csrc/%.hip $(HDRS)
 	@mkdir -p $(BUILD)
@@ -41,6 +42,11 @@ oracle/build/liboracle.so: oracle/gsdr_oracle.c oracle/gsdr_oracle.h gsdr_amd/cs
 	@mkdir -p oracle/build
 	$(CC) $(OFLAGS) -shared oracle/gsdr_oracle.c -o $@ -lm -lpthread
 
+# Reference-run libraries (oracle/_ref/, never committed): the reference's own kernel text compiled for the host, the
+# source of tests/golden/ref_*.npz. Does nothing, successfully, where the reference or the CUDA headers are absent.
+refhost:
+	$(PYTHON) oracle/refhost/build_ref.py
+
 # C++ host example linking the C ABI
 examples: $(BUILD)/fm_receiver $(BUILD)/short_call_timer
 
@@ -53,6 +59,6 @@ $(BUILD)/short_call_timer: examples/short_call_timer.cpp gsdr_amd/libgsdr.so $(H
 	$(HIPCC) -O2 -std=c++17 -Iinclude $< -Lgsdr_amd -lgsdr -Wl,-rpath,'$$ORIGIN/../gsdr_amd' -o $@
 
 clean:
-	rm -rf $(BUILD) gsdr_amd/libgsdr.so oracle/build
+	rm -rf $(BUILD) gsdr_amd/libgsdr.so oracle/build oracle/_ref
 
-.PHONY: all clean examples probes
+.PHONY: all clean examples probes refhost

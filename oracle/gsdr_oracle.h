@@ -2,14 +2,16 @@
  * gsdr CPU oracle -- TEST INFRASTRUCTURE ONLY.
  *
  * A scalar C restatement of the reference's hot-path semantics (kernrj/gsdr, read as text; the
- * reference itself cannot be built here: it needs nvcc/CUDA and a CMake-generated gsdr_export.h).
+ * reference as a whole cannot be built without nvcc/CUDA).
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library, and
  * only as the checker or the timed CPU baseline -- never as a product path.
  *
  * Parity pinning: see oracle/README.md and DESIGN.md section "Oracle". The oracle is checked against
  * (a) the known-answer tests of the reference's gtest suite, re-encoded with the kernel's actual
- * semantics, and (b) an independent float64 numpy restatement (tests/golden/). No executable output
- * of the reference exists, so transcendental results (atan2f, hypotf, sincos) are pinned by tolerance.
+ * semantics, (b) an independent float64 numpy restatement (tests/golden/), and (c) the outputs of the
+ * reference's own element-per-thread kernels compiled for the host (oracle/refhost/, tests/golden/ref_*.npz).
+ * Those run on the host's libm, not NVIDIA's, so transcendental results (atan2f, hypotf, sincos) stay
+ * pinned by tolerance.
  *
  * Complex arrays are interleaved float pairs (re, im), the layout of cuComplex / hipFloatComplex.
  * Range arguments [k0, k1) select which outputs to compute, so full-size inputs can be spot-checked.

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Generate the golden fixtures in tests/golden/*.npz.
 
-The reference (kernrj/gsdr) is CUDA-only and cannot be built or run in this image (no nvcc, no CUDA
-runtime, and its build needs a CMake-generated gsdr_export.h), and its gtest suite holds no numeric
-fixtures. The fixtures here are therefore an INDEPENDENT restatement of the reference's semantics in
+The reference (kernrj/gsdr) is CUDA-only and its gtest suite holds no numeric fixtures. What its
+element-per-thread kernels compute when compiled for the host is stored separately, in ref_*.npz
+(make_reference_vectors.py, oracle/refhost/); the NCO and the FM / AM chains cannot be run that way. The
+fixtures here are an INDEPENDENT restatement of the reference's semantics in
 numpy float64 (FIR, NCO, chains, discriminators) and exact integer / IEEE-float32 arithmetic (QPSK,
 QPSK256), written from the reference source (cited per case) -- not from the C oracle -- so that the
-oracle can be checked against something it does not share code with. Inputs are stored with the
+oracle can be checked against something it does not share code with; fir64 below is itself checked
+against the reference-run FIR vectors (tests/test_oracle_reference_vectors.py). Inputs are stored with the
 expected outputs. Re-run with:  python tests/golden/make_golden.py
 """
 from __future__ import annotations

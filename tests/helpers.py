@@ -272,3 +272,48 @@ def fm_conditioned_err(got, want, y_ref, s, g, eps=2e-6):
         allowed = eps * (kappa[:-1] + kappa[1:]) + 8.0 * 2.0 ** -149 / prod
     allowed = np.where(zero_pair, 1e-5 * np.pi, np.maximum(1e-5 * np.pi, np.nan_to_num(allowed, nan=np.inf)))
     return float(np.max(d / allowed)) if d.size else 0.0
+
+
+# Reference-run vectors (tests/golden/ref_*.npz, written by tests/golden/make_reference_vectors.py): what the
+# reference's own kernel text computes on the stored inputs, built with and without contraction of a * b + c.
+REF_BUILDS = ("contract", "nocontract")
+
+
+def ref_vectors(stem):
+    import os
+
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", stem + ".npz"), allow_pickle=False)
+
+
+def ref_pick(g, name, build):
+    """Output `name` of `build`: stored once, under `name`, where the two builds agree bit for bit."""
+    return g[name] if name in g.files else g[f"{name}__{build}"]
+
+
+def same_values(got, want):
+    """Bit identity of two float / complex / integer arrays, with every NaN equal to every NaN: IEEE 754 leaves the
+    sign and payload of a NaN that an operation produces open (x86 and the GPU differ, and so do two operand orders
+    on x86), everything else, the sign of a zero included, is compared bitwise. Returns the number of differing
+    elements (0 passes), or -1 for a dtype or shape mismatch."""
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    if got.dtype != want.dtype or got.shape != want.shape:
+        return -1
+    if got.dtype.kind not in "fc":
+        return int(np.count_nonzero(got != want))
+    g, w = got.view(np.float32), want.view(np.float32)
+    gn, wn = np.isnan(g), np.isnan(w)
+    return int(np.count_nonzero((gn != wn) | (~wn & (g.view(np.uint32) != w.view(np.uint32)))))
+
+
+def same_specials(got, want):
+    """The NaN pattern, the Inf pattern and the signs of the infinities agree, component by component."""
+    g = np.ascontiguousarray(got).view(np.float32)
+    w = np.ascontiguousarray(want).view(np.float32)
+    inf = np.isinf(w)
+    return bool(np.array_equal(np.isnan(g), np.isnan(w)) and np.array_equal(np.isinf(g), inf)
+                and np.array_equal(g[inf], w[inf]))
+
+
+def finite_elements(a):
+    a = np.asarray(a)
+    return np.isfinite(a.real) & np.isfinite(a.imag) if np.iscomplexobj(a) else np.isfinite(a)
