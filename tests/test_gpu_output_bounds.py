@@ -35,7 +35,7 @@ C64, F32 = torch.complex64, torch.float32
 # shapes of D = 1, 2, 4, 8; launch_other_d's contiguous-window and short polyphase tiles (3, 5, 6, 12, 16) and its
 # one-output-a-thread polyphase tiles (20, 64); the runtime-decimation kernel k_fir_rt (9, 13, 50); and the generic
 # kernel through launch_rt's D >= T branch (D = 64, T = 8).
-DISPATCH_CASES = [(D, 33) for D in (1, 2, 4, 8, 3, 5, 6, 12, 16, 20, 64, 9, 13, 50)] + [(64, 8)]
+DISPATCH_CASES = [(D, 33) for D in (1, 2, 4, 8, 3, 5, 6, 12, 16, 20, 48, 64, 9, 13, 50)] + [(64, 8)]
 
 # The generic kernel's other way in: at D = 4 the shortest filter whose tile no longer fits kMaxTileLds = 64 KiB
 # (fir_dispatch.hpp tap_span -> launch_generic), for the shape these output counts take.

@@ -50,11 +50,11 @@ def guarded_call(cuda, x, taps, D, n0, N):
 
 @pytest.mark.parametrize("n0", [0, 987654321, (1 << 32) + 5])
 @pytest.mark.parametrize("T", [1, 31, 127])
-@pytest.mark.parametrize("D", [1, 2, 3, 4, 5, 6, 8, 9, 13, 16, 20, 64])
+@pytest.mark.parametrize("D", [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 13, 16, 20, 24, 32, 40, 48, 50, 64])
 def test_parity_with_oracle(cuda, D, T, n0):
-    """Every dispatch class (contiguous absolute D = 1, 3, 5; anchored polyphase with R > 1 (2, 4, 6, 8, 16) and
-    R = 1 (20, 64); runtime-D 9, 13) against oracle.chain_fir. Measured maximum over all cases: see DESIGN.md
-    section 6."""
+    """Every decimation with a row of its own (contiguous absolute D = 1, 3, 5, 7; anchored polyphase with R > 1
+    (2, 4, 6, 8, 10, 12, 16) and R = 1 (20, 24, 32, 40, 48, 64)) and runtime-D 9, 13, 50 against oracle.chain_fir.
+    Measured maximum over all cases: see DESIGN.md section 6."""
     N = N_SMALL
     x = signal((N - 1) * D + T, seed=D * T)
     taps = taps_for(T)
